@@ -587,8 +587,26 @@ bool mb_exited(const DevCtx &c) { return __atomic_load_n(&c.h_mb[16], __ATOMIC_A
 
 int mb_wait(DevCtx &c, uint32_t seq, std::chrono::steady_clock::time_point t0);
 
+// The resident kernel runs on a non-blocking stream and serves a posted
+// request at once, so nothing orders its reads and writes of DEVICE memory
+// after work queued earlier on the NULL stream (a hipMemset of the
+// destination, a copy into the source) -- work the launched paths, on the
+// blocking c.stream, are ordered after.  A request that touches device memory
+// waits for it first: one stream query when nothing is pending.  (The wait
+// does not cover the mailbox's own stream; a marker it puts behind the
+// resident kernel makes the kernel leave, and the request relaunches it.)
+int mb_after_null_stream() {
+  const hipError_t q = hipStreamQuery(nullptr);
+  if (q == hipSuccess) return HDFS_CRC32C_OK;
+  (void)hipGetLastError();
+  HIPCHK(hipStreamSynchronize(nullptr));
+  return HDFS_CRC32C_OK;
+}
+
 int mailbox_call(DevCtx &c, int mode, uint32_t len, uint32_t cs, uint32_t reg0, bool be, int ctype,
                  const uint8_t *dsrc, const uint8_t *hsrc, const uint8_t *hcrc, uint32_t crc_bytes) {
+  if (dsrc)
+    if (const int rc = mb_after_null_stream()) return rc;
   const uint32_t seq = ++c.small_seq;
   const auto ta = std::chrono::steady_clock::now();
   if (c.mb_alive && mb_exited(c)) c.mb_alive = false;  // idled out since the last call
@@ -629,6 +647,7 @@ int mailbox_call(DevCtx &c, int mode, uint32_t len, uint32_t cs, uint32_t reg0, 
 // c.mb_on.
 int mailbox_copy(DevCtx &c, const CopyEntry *e, uint32_t n) {
   if (!n || n > kCopyPiecesMax) return fail(HDFS_CRC32C_EINVAL, "mailbox copy of %u pieces", n);
+  if (const int rc = mb_after_null_stream()) return rc;
   const uint32_t seq = ++c.small_seq;
   if (c.mb_alive && mb_exited(c)) c.mb_alive = false;
   if (!c.mb_alive) {

@@ -500,6 +500,9 @@ int hdfs_crc32c_host_free(void *p);
  * leave at once (it watches its AQL queue's write index), and the next call
  * relaunches it: such work waits microseconds, not idle_ms (round 5's
  * 50 ms stalls, profiles/r06/r6c_mb_share.json vs r6e_mb_share.json).
+ * A request that touches device memory (a reader's delivery, the CRC of
+ * device bytes) is ordered after work queued earlier on the NULL stream, as
+ * the launched paths are: it waits for that work before it is posted.
  * One mailbox per device (EBUSY-style HDFS_CRC32C_EINVAL for a second). */
 typedef struct hdfs_crc32c_mailbox hdfs_crc32c_mailbox;
 int hdfs_crc32c_mailbox_create(hdfs_crc32c_mailbox **mb, uint32_t idle_ms);

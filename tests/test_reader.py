@@ -297,6 +297,38 @@ def test_gpu_reader_through_mailbox(engine, oracle):
 
 
 @pytest.mark.gpu
+def test_gpu_mailbox_delivery_follows_null_stream_fill(engine, oracle):
+    """A delivery through the open mailbox is ordered after work queued
+    earlier on the NULL stream, as a launched delivery is: the destination is
+    filled (hipMemset of 256 MiB on the NULL stream, not waited for) right
+    before a reader's 64 KiB delivery, and the delivered bytes win -- the
+    resident kernel, on a non-blocking stream, once copied while the fill was
+    still queued and the fill then landed over the head of the read."""
+    dl = [65536] * 4
+    s, _ = build_stream(oracle.crc32c, 2, 512, CSUM_CRC32C, dl, seed=45)
+    keep, p = _dev(engine, s, 1)
+    co, rl = 0, 65536
+    want = oracle.read_packets(s, co, rl)
+    assert len(want[3]) == rl
+    dst = engine.DeviceBuffer(256 << 20)
+    with engine.Mailbox(idle_ms=50) as mb:
+        for rep in range(3):
+            c0 = mb.stats()[0]
+            rd = engine.Reader(p, len(s), co, rl)
+            try:
+                dst.fill(0xA5)
+                rc, pk, used, got = rd.next([(dst.ptr, rl)])
+            finally:
+                rd.close()
+            assert (rc, got) == (want[0], rl), rep
+            assert dst.download(got).tobytes() == want[3], rep
+            assert dst.download(16, offset=rl).tobytes() == b"\xa5" * 16, rep
+            assert mb.stats()[0] - c0 >= 1, rep  # served by the resident kernel
+    dst.free()
+    keep.free()
+
+
+@pytest.mark.gpu
 def test_gpu_reader_records_or_stream_run_out(engine, oracle):
     """A read the reader cannot complete -- its record array (max_pkts) or
     the stream ends first -- delivers what the oracle's read loop delivers

@@ -24,18 +24,18 @@ step() { local name=$1; shift; "$@"; local rc=$?; echo "[$name] rc=$rc" >&2; cas
 has t && step tests timeout -k 10 900 python -u -m pytest tests -m gpu -x -q -p no:cacheprovider --timeout 300 --timeout-method thread > ${O}_tests.log 2>&1
 has t && tail -2 ${O}_tests.log
 has t && step smoke timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()"
-has b && step bench timeout -k 10 600 python bench.py > ${O}_bench.json 2> ${O}_bench.err
+has b && step bench timeout -k 10 600 python bench.py --full > ${O}_bench.json 2> ${O}_bench.err
 has b && cat ${O}_bench.json
-# the driver's own command under the profiler: its bench line and its trace
+# the same full bench under the profiler: its bench line and its trace
 # come from one process (tools/trace_vs_line.py compares the timed launches)
-has b && step prof timeout -k 10 900 rocprofv3 --kernel-trace --stats -d ${O}_prof -o run --output-format csv -- python3 bench.py > ${O}_prof.log 2>&1
+has b && step prof timeout -k 10 900 rocprofv3 --kernel-trace --stats -d ${O}_prof -o run --output-format csv -- python3 bench.py --full > ${O}_prof.log 2>&1
 has b && step trace_vs_line python tools/trace_vs_line.py ${O}_prof/run_kernel_trace.csv ${O}_prof.log ${O}_trace_vs_line.json
 has b && grep -h crc32c_tiles ${O}_prof/run_kernel_stats.csv | cut -c1-200
 has p && step pmc timeout -k 10 900 python tools/pmc_traffic.py ${RND} > ${O}_pmc.json 2> ${O}_pmc.err
 has p && cat ${O}_pmc.json
-has p && step torchrun timeout -k 10 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29533 bench.py --gpus 1 --steps 5 --warmup 1 --no-cpu > ${O}_torchrun.json 2> ${O}_torchrun.err
+has p && step torchrun timeout -k 10 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29533 bench.py --gpus 1 --steps 5 --warmup 1 --full --no-cpu > ${O}_torchrun.json 2> ${O}_torchrun.err
 has p && cat ${O}_torchrun.json
-has p && step c4 timeout -k 10 600 python bench.py --config C4 --steps 10 --no-cpu > ${O}_c4.json 2> ${O}_c4.err
+has p && step c4 timeout -k 10 600 python bench.py --config C4 --steps 10 --full --no-cpu > ${O}_c4.json 2> ${O}_c4.err
 has p && cat ${O}_c4.json
 has d && step dstream timeout -k 10 300 python tools/device_stream_bench.py > ${O}_dstream.json 2> ${O}_dstream.err
 has d && cat ${O}_dstream.json
