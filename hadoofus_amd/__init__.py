@@ -5,6 +5,8 @@ The product is the C-ABI shared library ``hadoofus_amd/lib/libhadoofus_crc32c.so
 mirror of that ABI used by the tests and bench; it has no compute of its own
 and no fallback: if the library or a gfx950 device is missing, calls fail.
 Tuning knobs live only in the separate diagnostic build (tools/diaglib.py).
+The MD5CRC block / file checksums (include/hadoofus_md5crc.h) live in the
+companion library libhadoofus_md5crc.so, loaded on first use (md5crc.py).
 """
 from .abi import (  # noqa: F401
     LIB_PATH, bind_product, bind_diag, CSUM_NULL, CSUM_CRC32, CSUM_CRC32C, ERR_BAD_CHECKSUM, ERR_CRC_LEN,
@@ -15,6 +17,9 @@ from .abi import (  # noqa: F401
     composite_crcs, compute_host, verify_host, PinnedBuffer, corrupt, fill_splitmix64, stream_create,
     stream_sync, device_info, init, bound_device, device_sync, load, stream_crc_dev, stream_ex,
     verify_crcdata, VerifyJob, VerifyBlocksJob, Reader, read_packets_fd, EIO,
+)
+from .md5crc import (  # noqa: F401  (binds nothing until first use)
+    FileChecksum, block_md5crcs, file_checksum, file_checksum_from_blocks, md5_host,
 )
 
 __all__ = [n for n in dir() if not n.startswith("_")]

@@ -27,6 +27,10 @@ DIAG_SOURCES = SOURCES + ["crc32c_probes.hip"]
 HEADERS = ["crc32c_internal.h", "crc32c_tables.h", "crc32c_packets.h", "crc32c_engine.h", "crc32c_frame.h",
            "crc32c_hostpin.h", "crc32c_diag_ep.h", "exports.map"]
 PUBLIC = ["hadoofus_crc32c.h", "crc32c.h", "hadoofus_crc32c_diag.h"]
+MD5CRC_LIB = os.path.join(LIBDIR, "libhadoofus_md5crc.so")
+MD5CRC_SOURCES = ["md5crc_kernels.hip", "md5crc.cpp"]
+MD5CRC_HEADERS = ["md5_core.h", "md5crc_internal.h", "md5crc_exports.map"]
+MD5CRC_PUBLIC = ["hadoofus_md5crc.h", "hadoofus_crc32c.h"]
 ARCH = os.environ.get("HADOOFUS_OFFLOAD_ARCH", "gfx950")
 
 
@@ -37,12 +41,12 @@ def _hipcc():
     raise RuntimeError("hipcc not found")
 
 
-def _stale(lib, sources):
+def _stale(lib, sources, headers=HEADERS, public=PUBLIC, others=()):
     if not os.path.exists(lib):
         return True
     t = os.path.getmtime(lib)
-    deps = [os.path.join(CSRC, f) for f in sources + HEADERS] + [os.path.join(INCLUDE, f) for f in PUBLIC]
-    return any(os.path.getmtime(d) > t for d in deps)
+    deps = [os.path.join(CSRC, f) for f in sources + headers] + [os.path.join(INCLUDE, f) for f in public]
+    return any(os.path.getmtime(d) > t for d in deps + list(others))
 
 
 def _cmd(out, sources, extra):
@@ -57,9 +61,17 @@ def _cmd(out, sources, extra):
             f"-I{INCLUDE}", f"-I{CSRC}"] + extra + ["-o", out] + [os.path.join(CSRC, f) for f in sources]
 
 
+def _md5crc_cmd(out):
+    return [_hipcc(), f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC", "-shared", "-Wall",
+            "-Wno-unused-function", f"-Wl,--version-script={os.path.join(CSRC, 'md5crc_exports.map')}",
+            f"-I{INCLUDE}", f"-I{CSRC}", "-o", out] + [os.path.join(CSRC, f) for f in MD5CRC_SOURCES] + [
+            f"-L{LIBDIR}", "-lhadoofus_crc32c", "-Wl,-rpath,$ORIGIN"]
+
+
 def build(force=False, verbose=False, diag=True):
     """Build the release library (and, with diag=True, the diagnostic one,
-    in parallel).  Returns the release library's path."""
+    in parallel), then the MD5CRC companion.  Returns the release library's
+    path."""
     os.makedirs(LIBDIR, exist_ok=True)
     jobs = []
     if force or _stale(LIB, SOURCES):
@@ -75,6 +87,13 @@ def build(force=False, verbose=False, diag=True):
         if p.wait() != 0:
             raise subprocess.CalledProcessError(p.returncode, cmd)
         os.replace(out + ".tmp", out)
+    # the companion links against the release library, so after it is in place
+    if force or _stale(MD5CRC_LIB, MD5CRC_SOURCES, MD5CRC_HEADERS, MD5CRC_PUBLIC, [LIB]):
+        cmd = _md5crc_cmd(MD5CRC_LIB + ".tmp")
+        if verbose:
+            print(" ".join(cmd), file=sys.stderr)
+        subprocess.check_call(cmd)
+        os.replace(MD5CRC_LIB + ".tmp", MD5CRC_LIB)
     return LIB
 
 
