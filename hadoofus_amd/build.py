@@ -25,7 +25,7 @@ DIAG_LIB = os.path.join(LIBDIR, "libhadoofus_crc32c_diag.so")
 SOURCES = ["crc32c_kernels.hip", "crc32c_engine.cpp", "crc32c_packets.cpp"]
 DIAG_SOURCES = SOURCES + ["crc32c_probes.hip"]
 HEADERS = ["crc32c_internal.h", "crc32c_tables.h", "crc32c_packets.h", "crc32c_engine.h", "crc32c_frame.h",
-           "crc32c_hostpin.h", "crc32c_diag_ep.h", "exports.map"]
+           "crc32c_hostpin.h", "crc32c_diag_ep.h", "crc32c_deal.h", "exports.map"]
 PUBLIC = ["hadoofus_crc32c.h", "crc32c.h", "hadoofus_crc32c_diag.h"]
 MD5CRC_LIB = os.path.join(LIBDIR, "libhadoofus_md5crc.so")
 MD5CRC_SOURCES = ["md5crc_kernels.hip", "md5crc.cpp"]

@@ -20,6 +20,7 @@
 
 #include <unistd.h>
 
+#include "crc32c_deal.h"
 #include "crc32c_engine.h"
 #include "crc32c_tables.h"
 #ifdef HDFS_CRC32C_DIAG
@@ -394,7 +395,9 @@ bool device_accessible(const void *p) {
   return a.devicePointer != nullptr;
 }
 
-uint32_t tile_tune() { return (kDiag ? g_store_policy : 0u) | (g_group_shift << 8) | (g_xcd_major << 12); }
+uint32_t tile_tune(uint32_t pool_min) {
+  return tune_pack(kDiag ? g_store_policy : 0u, g_group_shift, g_xcd_major, pool_min);
+}
 
 int launch_verify_dyn(DevCtx &c, const SegDev *d_segs, const GridSummary *dyn, uint64_t rounds_ub, uint64_t gtiles_ub,
                       uint32_t *d_fb, unsigned long long *d_mism, uint32_t *d_gctr, hipStream_t st, int ctype,
@@ -411,8 +414,7 @@ int launch_verify_dyn(DevCtx &c, const SegDev *d_segs, const GridSummary *dyn, u
   // back to searching the table when it is not
   const hipError_t le = launch_tiles(kModeVerify, 3, g_nt_loads, 3, 1, 1024, grid, d_segs, 0, 0, 0,
                                      c.d_tab_main_t[ctype], d_fb, d_mism, nullptr,
-                                     (kDiag ? g_store_policy : 0u) | (g_group_shift << 8) | (g_xcd_major << 12), d_gctr,
-                                     st, copy ? 1 : 0, 1, dyn, 0u, 1);
+                                     tile_tune(), d_gctr, st, copy ? 1 : 0, 1, dyn, 0u, 1);
   if (le == hipErrorInvalidValue) return fail(HDFS_CRC32C_EINVAL, "verify kernel shape not built");
   HIPCHK(le);
   return HDFS_CRC32C_OK;
@@ -485,8 +487,8 @@ int launch_all(DevCtx &c, int mode, const SegDev *d_segs, uint32_t nseg, uint64_
     const int kmode = (kDiag && mode == kModeVerify && g_store_policy == 4) ? int(kModeLoadOnly) : mode;
     const hipError_t le = launch_tiles(kmode, order, nt, depth, streams, block, grid, d_segs, nseg, rounds,
                                        mtiles, c.d_tab_main_t[ctype], d_fb, d_mism, kDiag ? g_diag : nullptr,
-                                       (kDiag ? g_store_policy : 0u) | (g_group_shift << 8) | (g_xcd_major << 12),
-                                       d_gctr, st, copy ? 1 : 0, una ? 1 : 0, nullptr, order >= 3 ? utiles : 0u);
+                                       tile_tune(), d_gctr, st, copy ? 1 : 0, una ? 1 : 0, nullptr,
+                                       order >= 3 ? utiles : 0u);
     if (le == hipErrorInvalidValue)
       return fail(HDFS_CRC32C_EINVAL, "tiled kernel shape (order %d, nt %d, depth %d, streams %d, block %d) is not built",
                   order, nt, depth, streams, block);

@@ -387,11 +387,11 @@ uint32_t uniform_tiles(const SegDev *segs, size_t n);
 int launch_verify_dyn(DevCtx &c, const SegDev *d_segs, const GridSummary *dyn, uint64_t rounds_ub, uint64_t gtiles_ub,
                       uint32_t *d_fb, unsigned long long *d_mism, uint32_t *d_gctr, hipStream_t st, int ctype,
                       bool copy);
-// The tiled kernel's tune word (schedule-3 group shift, XCD dealing; the
-// diagnostic build's store policy).
-uint32_t tile_tune();
+// The tiled kernel's tune word (crc32c_deal.h: schedule-3 group shift, XCD
+// dealing, the diagnostic build's store policy; pool_min 0: 32).
+uint32_t tile_tune(uint32_t pool_min = 0u);
 // spec_verify_kernel: rounds per wave from which the global pool is used
-// (tune bits 23:16 of the tiled kernel; 0 there means 32)
+// (the tune word's pool minimum)
 extern uint32_t g_spec_pool_min;
 // copy_pieces_kernel table launches: fewest units per workgroup; piece table
 // in device memory (1) or read from pinned memory (0)

@@ -21,6 +21,7 @@
 //      (CRC linearity, src/crc32c_sse42.c:270-319 uses the same algebra).
 #include <hip/hip_runtime.h>
 
+#include "crc32c_deal.h"
 #include "crc32c_frame.h"
 #include "crc32c_internal.h"
 
@@ -188,8 +189,8 @@ DEV void spec_run_contribute(SpecCtl *ctl, uint8_t *hdone, uint32_t seq, uint32_
 }
 
 // LDS words of the per-run completion (BATCH): [0, 16) tiles of run r this
-// workgroup has verified, [16, 32) tiles of run r it owns (kEarlyOff: r has
-// pool tiles, not published), [32, 48) run r's target (workgroups + header
+// workgroup has verified, [16, 32) tiles of run r it owns (static_owned(),
+// crc32c_deal.h; kEarlyOff: r has pool tiles, not published), [32, 48) run r's target (workgroups + header
 // groups), [48] the owned tiles' sum, [49] per-run completion on
 constexpr uint32_t kEarlyWords = 50, kEarlyOff = 0xFFFFFFFFu;
 
@@ -197,8 +198,9 @@ template <bool BATCH>
 struct SpecTabT {
   const CAS SpecTabData *p;
   uint32_t *e;  // BATCH: the per-run completion words (LDS, kEarlyWords)
-  // per-run completion on for this wave: the owned tiles the prologue
-  // restated from the schedule add up to the wave's own static tickets
+  // per-run completion on for this wave: the owned tiles the prologue took
+  // from static_deal() add up to the static tickets tiles_run took from it
+  // (a guard that both sites passed the same launch to the one function)
   DEV uint32_t early_ok(uint32_t nk) const {
     if constexpr (BATCH) return rfl(e[49] != 0u && e[48] == nk ? 1u : 0u);
     return 0u;
@@ -316,15 +318,16 @@ struct Cursor {
 //    split leaves the oldest waves idle for the last ~15 % of the kernel.
 //    The LDS atomic counts in lgkmcnt, never in the vmcnt that orders the
 //    data prefetch.
-//  ORDER 2 (two-phase): as ORDER 1 over the first kPhase1Num/kPhase1Den of
-//    the rounds; the remaining tiles form a global pool of kUnit-tile units
+//  ORDER 2 (two-phase): as ORDER 1 over the first phase1() (crc32c_deal.h)
+//    of the rounds; the remaining tiles form a global pool of kUnit-tile units
 //    that workgroups claim with one global atomic each once their own slice
 //    is done (published to the workgroup's other waves through an LDS slot).
 //    The pool absorbs the cross-workgroup / cross-XCD speed spread; its
 //    atomics only happen at the end, off the hot loop.
 //  ORDER 3 (interleaved two-phase): as ORDER 2, but the static phase deals
 //    groups of 2^gshift consecutive tiles round-robin over the workgroups
-//    (workgroup b takes groups b, b+G, b+2G, ...), so at any moment the
+//    (workgroup b takes groups b, b+G, b+2G, ...; static_deal() of
+//    crc32c_deal.h, with its XCD forms), so at any moment the
 //    whole grid reads one contiguous window of memory instead of G separate
 //    streams; the read probes of crc32c_probes.hip measured this shape
 //    faster on MI355X HBM.  Groups of >= 4 tiles own whole 128-B lines of
@@ -354,7 +357,6 @@ struct Cursor {
 //    5-6.5 % even inside an L2-sized window; profiles/r03/exp_columns*.json).
 constexpr uint32_t kUnitMaxShift = 8, kUnitMinShift = 4;
 constexpr uint32_t kColBytes = 128;  // ORDER 7: bytes of each chunk per round
-constexpr uint32_t kColShift = 2;    // ORDER 7: log2 tiles per ticket (32 chunks)
 constexpr uint32_t kSlots = 8;  // LDS slots for published units
 // Compute gather (schedule 3, RUN 2): the CRCs of an 8-tile group, finished
 // by up to eight waves of the workgroup, collect in one of kGatherSlots LDS
@@ -366,10 +368,6 @@ constexpr uint32_t kSlots = 8;  // LDS slots for published units
 #endif
 static_assert((HDFS_GATHER_SLOTS & (HDFS_GATHER_SLOTS - 1)) == 0, "gather slots: a power of two");
 constexpr uint32_t kGatherSlots = HDFS_GATHER_SLOTS, kGatherWords = kGatherSlots * 65;
-#ifndef HDFS_PHASE1_NUM  // A/B builds only (-DHDFS_PHASE1_NUM=n)
-#define HDFS_PHASE1_NUM 23
-#endif
-constexpr uint64_t kPhase1Num = HDFS_PHASE1_NUM, kPhase1Den = 25;  // 92 % static
 
 struct Sched {
   uint64_t r1;       // ORDER 0: end of the wave's round slice
@@ -404,17 +402,12 @@ DEV uint32_t grab(const Sched &w) {
   return rfl(k);
 }
 
-// Ticket -> global tile.  Tickets below nk are the workgroup's own slice;
-// later tickets walk the pool unit by unit.
+// Ticket -> global tile.  Tickets below nk are the workgroup's own slice
+// (static_tile(), crc32c_deal.h); later tickets walk the pool unit by unit.
 template <int ORDER>
 DEV bool ticket_tile(const Sched &w, uint32_t t, uint64_t &g) {
   if (t < w.nk) {
-    if (ORDER == 4 || ORDER == 7)
-      g = (w.gfirst + uint64_t(t) * w.gstride) << w.gshift;
-    else if (ORDER == 3)
-      g = ((w.gfirst + uint64_t(t >> w.gshift) * w.gstride) << w.gshift) + (t & ((1u << w.gshift) - 1u));
-    else
-      g = w.gfirst + t;
+    g = static_tile(ORDER, w.gfirst, w.gstride, w.gshift, t);
     return true;
   }
   if (ORDER < 2) return false;
@@ -448,6 +441,17 @@ DEV Cursor locate(Tab segs, uint32_t s, uint64_t g) {
   return Cursor{rfl(s), rfl(static_cast<uint32_t>(g - segs[s].mtile_start)), 0u, true};
 }
 
+// Global tile g -> (segment, tile) by a binary search of the table.
+template <class Tab>
+DEV Cursor search_tile(Tab segs, uint32_t nseg, uint64_t g) {
+  uint32_t lo = 0, hi = nseg;
+  while (hi - lo > 1) {
+    const uint32_t mid = (lo + hi) >> 1;
+    if (segs[mid].mtile_start <= g) lo = mid; else hi = mid;
+  }
+  return locate(segs, lo, g);
+}
+
 // Global tile g -> cursor, from the current cursor c (whose segment's hot
 // fields are sh).  Pool tiles may lie behind the slice or far ahead of it (a
 // table of thousands of packet-sized segments: a forward walk from the slice
@@ -457,14 +461,7 @@ template <int ORDER, class Tab>
 DEV Cursor find_tile(const Cursor c, const SegHot &sh, Tab segs, uint32_t nseg, const Sched &w, uint64_t g) {
   const uint64_t end = sh.mtile_start + sh.main_tiles;
   if (w.ut && (g < sh.mtile_start || g >= end)) return ulocate(w, g);
-  if (g < sh.mtile_start || g >= end + (ORDER >= 3 ? 0u : kWalkTiles)) {
-    uint32_t lo = 0, hi = nseg;
-    while (hi - lo > 1) {
-      const uint32_t mid = (lo + hi) >> 1;
-      if (segs[mid].mtile_start <= g) lo = mid; else hi = mid;
-    }
-    return locate(segs, lo, g);
-  }
+  if (g < sh.mtile_start || g >= end + (ORDER >= 3 ? 0u : kWalkTiles)) return search_tile(segs, nseg, g);
   if (g < end)  // same segment (the common case): from the cached fields, no table read
     return Cursor{c.seg, rfl(static_cast<uint32_t>(g - sh.mtile_start)), 0u, true};
   return locate(segs, c.seg, g);
@@ -1321,10 +1318,8 @@ DEV void tiles_run(uint32_t *lds, const Tab sg, const SegDev *__restrict__ segs,
   // GATHER 1: the compute gather (RUN 2); 2: the lazy gather (RUN 3)
   static_assert(GATHER == 0 || (MODE == kModeCompute && ORDER == 3 && S == 1), "gather: compute, schedule 3");
   LaneConst L;
-  // tune: [7:0] store policy (diagnostic build), [11:8] ORDER-3 group shift,
-  // [13:12] ORDER-3 dealing: 0 plain, 1 XCD-major, 2 XCD-split, [23:16] pool
-  // threshold in rounds per wave (uniform: SGPR)
-  L.store_policy = EP::policy(tune & 0xffu);
+  // tune (crc32c_deal.h) is uniform: SGPR
+  L.store_policy = EP::policy(tune_policy(tune));
   L.lane = threadIdx.x & 63u;
   L.hsel = (L.lane >> 3) & 1u;                              // load: odd sub-chunk of each 1 KiB
   L.loff = 16u * (4u * (L.lane & 7u) + (L.lane >> 4));      // load: byte offset in the sub-chunk
@@ -1363,55 +1358,25 @@ DEV void tiles_run(uint32_t *lds, const Tab sg, const SegDev *__restrict__ segs,
     if (r0 < w.r1) {
       const uint64_t g = tile_at_round(sg, nseg, r0, total_tiles);
       if (g < total_tiles) {
-        uint32_t lo = 0, hi = nseg;
-        while (hi - lo > 1) {
-          const uint32_t mid = (lo + hi) >> 1;
-          if (sg[mid].mtile_start <= g) lo = mid; else hi = mid;
-        }
-        c0 = locate(sg, lo, g);
+        c0 = search_tile(sg, nseg, g);
         c0.valid = sg[c0.seg].round_start + uint64_t(c0.tile) * (sg[c0.seg].chunk_size / kRoundBytes) < w.r1;
       }
     }
   } else {
-    // tune bits 23:16: rounds per wave from which the pool is used (0: 32)
-    const uint32_t pmin = (tune >> 16) & 0xffu;
-    const bool pool = ORDER >= 2 && total_rounds >= uint64_t(pmin ? pmin : 32u) * nwaves * S;
+    const uint32_t tlanes = nwaves * S;
     if (ORDER >= 3) {
-      // static phase: whole groups only; the pool takes the rest
-      // ORDER 4: 2^gshift tiles per run (8 in the diagnostic default; 4 = one
-      // 128-B CRC line per run), at most 8 (one register of CRCs)
-      w.gshift = ORDER == 7 ? kColShift : ORDER == 4 ? min((tune >> 8) & 15u, 3u) : (tune >> 8) & 15u;
-      if (ORDER == 4) L.rmask = (1u << w.gshift) - 1u;
-      const uint64_t ngroups = (pool ? total_tiles * kPhase1Num / kPhase1Den : total_tiles) >> w.gshift;
-      // tune bit 12: XCD-major dealing.  Workgroups are dispatched to the 8
-      // XCDs round-robin (XCD = blockIdx % 8), so with the plain dealing the
-      // groups an XCD works on at one time are 8 apart; dealing by the
-      // virtual id (blockIdx % 8) * (G / 8) + blockIdx / 8 gives each XCD
-      // (and its L2) a contiguous run of G / 8 groups per sweep step.
-      // tune bits 13:12 = 2: XCD-split dealing.  XCD x owns the contiguous
-      // eighth [x * ngx, (x + 1) * ngx) of the static groups and deals it over
-      // its G/8 workgroups, so the 8 XCDs sweep 8 separate windows (their
-      // compute-mode CRC writes land in 8 separate regions at any moment);
-      // the < 8 leftover groups go to the pool.
-      const uint32_t b = blockIdx.x, G = gridDim.x, xm = (tune >> 12) & 3u;
-      if (xm == 2u && (G % 8u) == 0 && ngroups >= 8ull * (G / 8u)) {
-        const uint64_t ngx = ngroups / 8u;
-        const uint32_t G8 = G / 8u, l = b / 8u;
-        w.gfirst = (b % 8u) * ngx + l;
-        w.gstride = G8;
-        w.nk = static_cast<uint32_t>(((ngx - 1 - l) / G8 + 1) << (ORDER == 4 || ORDER == 7 ? 0u : w.gshift));
-        w.p2first = (ngx * 8u) << w.gshift;
-      } else {
-        w.gfirst = xm != 0u && (G % 8u) == 0 ? (b % 8u) * (G / 8u) + b / 8u : b;
-        w.gstride = gridDim.x;
-        // tickets of the static phase: tiles (ORDER 3) or whole groups (ORDER 4)
-        w.nk = ngroups > w.gfirst
-                   ? static_cast<uint32_t>(((ngroups - 1 - w.gfirst) / gridDim.x + 1) << (ORDER == 4 || ORDER == 7 ? 0u : w.gshift))
-                   : 0u;
-        w.p2first = ngroups << w.gshift;
-      }
+      // the static phase of the interleaved schedules (crc32c_deal.h)
+      const Deal<uint64_t> d =
+          static_deal<uint64_t>(tune, ORDER, total_tiles, total_rounds, tlanes, blockIdx.x, gridDim.x);
+      w.gshift = d.gshift;
+      if (ORDER == 4) L.rmask = (1u << w.gshift) - 1u;  // 2^gshift tiles per run
+      w.gfirst = d.gfirst;
+      w.gstride = d.gstride;
+      w.nk = d.nk();
+      w.p2first = d.p2first;
     } else {
-      const uint64_t r_static = pool ? total_rounds * kPhase1Num / kPhase1Den : total_rounds;
+      const bool pool = ORDER >= 2 && pool_on(tune, total_rounds, tlanes);
+      const uint64_t r_static = pool ? phase1(total_rounds) : total_rounds;
       const uint64_t b0 = rfl64(r_static * blockIdx.x / gridDim.x);
       const uint64_t b1 = rfl64(r_static * (blockIdx.x + 1) / gridDim.x);
       w.gfirst = tile_at_round(sg, nseg, b0, total_tiles);
@@ -1433,16 +1398,8 @@ DEV void tiles_run(uint32_t *lds, const Tab sg, const SegDev *__restrict__ segs,
       uint64_t g;
       const uint32_t tk = grab(w);
       if (ticket_tile<ORDER>(w, tk, g)) {
-        if (w.ut) {
-          cur[0][s] = ulocate(w, g);
-        } else {
-          uint32_t lo = 0, hi = nseg;
-          while (hi - lo > 1) {
-            const uint32_t mid = (lo + hi) >> 1;
-            if (sg[mid].mtile_start <= g) lo = mid; else hi = mid;
-          }
-          cur[0][s] = locate(sg, lo, g);
-        }
+        if (w.ut) cur[0][s] = ulocate(w, g);
+        else cur[0][s] = search_tile(sg, nseg, g);
         cur[0][s].grp = tk >> 3;
       }
     }
@@ -3312,7 +3269,7 @@ __global__ __launch_bounds__(1024) void spec_verify_kernel(SpecArgs a) {
       stores_done();
     }
     if (BATCH && r < kSpecRunsMax) ecnt[r] = 0u;  // per-run completion: tiles counted per run
-    if (BATCH && r == 0) ecnt[49] = 0u;           // (off until every wave has restated the dealing)
+    if (BATCH && r == 0) ecnt[49] = 0u;           // (off until every wave has written what it owns)
   }
   __syncthreads();
   stamp(1);
@@ -3331,44 +3288,32 @@ __global__ __launch_bounds__(1024) void spec_verify_kernel(SpecArgs a) {
   d.stride = rfl64(run.stride);
   d.off0 = rfl64(run.off0);
   d.seq0 = rfl64(run.seq0);
+  // the tiled launch: schedule 3 over the runs' packets, one stream per wave
+  // (what the per-run completion below and tiles_run deal from)
+  constexpr int kBlock = 1024, kStreams = 1;
+  const uint64_t tiles = uint64_t(d.count) * d.T, rounds = tiles * (a.cs / kRoundBytes);
+  const uint32_t tlanes = gridDim.x * (kBlock / 64) * kStreams;
   if (BATCH && d.eligible) {
     // Per-run completion (a coalesced batch, a.early): the tiles this
-    // workgroup owns of each run -- tiles_run's schedule 3 dealing restated
+    // workgroup owns of each run, from the static_deal() (crc32c_deal.h)
+    // that tiles_run fills its schedule from, over the same launch
     // (static groups of 2^gshift tiles, gfirst + i * gstride; the pool takes
     // tiles from p2first on) -- each run's target, and the runs with pool
     // tiles, which are not published.  Every wave writes the same words
-    // (lane r: run r) before its own tiles; tiles_run checks the
-    // restatement against the wave's own static tickets (early_ok) before
-    // any tile counts.  32-bit: a batch has < 2^31 tiles.
+    // (lane r: run r) before its own tiles; tiles_run checks their sum
+    // against the wave's own static tickets (early_ok: both sites passed the
+    // same launch) before any tile counts.  32-bit: a batch has < 2^31 tiles.
     const uint32_t cnt0 = rfl(rcount[0]);
-    const uint32_t per_t = cnt0 * d.T, ntl = per_t * nruns;
-    const uint32_t G = gridDim.x, b = blockIdx.x, pmin = (a.tune >> 16) & 0xffu;
-    const bool pool = uint64_t(ntl) * (a.cs / kRoundBytes) >= uint64_t(pmin ? pmin : 32u) * G * 16u;
-    const uint32_t gsh = (a.tune >> 8) & 15u, xm = (a.tune >> 12) & 3u;
-    const uint32_t ng = static_cast<uint32_t>((pool ? uint64_t(ntl) * kPhase1Num / kPhase1Den : ntl) >> gsh);
-    uint32_t gf, gst, nkg, p2;
-    if (xm == 2u && (G % 8u) == 0 && ng >= 8u * (G / 8u)) {
-      const uint32_t ngx = ng / 8u, G8 = G / 8u, l = b / 8u;
-      gf = (b % 8u) * ngx + l;
-      gst = G8;
-      nkg = (ngx - 1u - l) / G8 + 1u;
-      p2 = (ngx * 8u) << gsh;
-    } else {
-      gf = xm != 0u && (G % 8u) == 0 ? (b % 8u) * (G / 8u) + b / 8u : b;
-      gst = G;
-      nkg = ng > gf ? (ng - 1u - gf) / G + 1u : 0u;
-      p2 = ng << gsh;
-    }
-    auto below = [&](uint32_t x) -> uint32_t {  // this workgroup's static groups under group x
-      return x > gf ? min(nkg, (x - gf + gst - 1u) / gst) : 0u;
-    };
-    const bool on = a.early != 0u && nruns > 1u && (per_t & ((1u << gsh) - 1u)) == 0u &&
+    const uint32_t per_t = cnt0 * d.T, G = gridDim.x;
+    const Deal<uint32_t> dl =
+        static_deal<uint32_t>(a.tune, 3, static_cast<uint32_t>(tiles), rounds, tlanes, blockIdx.x, G);
+    const bool on = a.early != 0u && nruns > 1u && (per_t & ((1u << dl.gshift) - 1u)) == 0u &&
                     uint64_t(cnt0) * d.T * nruns < (1ull << 31);
     const uint32_t r = lane;
     uint32_t owned = 0, dis = 1;
     if (r < nruns) {
-      owned = (below(((r + 1u) * per_t) >> gsh) - below((r * per_t) >> gsh)) << gsh;
-      dis = (r + 1u) * per_t > p2 ? 1u : 0u;
+      owned = static_owned(dl, r * per_t, (r + 1u) * per_t);
+      dis = reaches_pool(dl, (r + 1u) * per_t) ? 1u : 0u;
       ecnt[16u + r] = dis ? kEarlyOff : owned;
       ecnt[32u + r] = G + (rcount[r] + 63u) / 64u;
     }
@@ -3581,10 +3526,9 @@ __global__ __launch_bounds__(1024) void spec_verify_kernel(SpecArgs a) {
   };
   if (hdr_first && j0 < ngroups) check(j0, h0);
   const SpecTabT<BATCH != 0> tab{(const CAS SpecTabData *)(a.tabs + blockIdx.x), ecnt};
-  const uint64_t tiles = uint64_t(d.count) * d.T;
-  tiles_run<kModeVerify, 3, 1, 3, 1, 1024, 1, COPY, 1, 0>(lds, tab, nullptr, d.count, tiles * (a.cs / kRoundBytes),
-                                                          tiles, a.fb, &ctl->mism, kDiag ? a.stamps : nullptr, a.tune,
-                                                          &ctl->gctr, nullptr, d.T, false);
+  tiles_run<kModeVerify, 3, 1, 3, kStreams, kBlock, 1, COPY, 1, 0>(lds, tab, nullptr, d.count, rounds, tiles, a.fb,
+                                                                   &ctl->mism, kDiag ? a.stamps : nullptr, a.tune,
+                                                                   &ctl->gctr, nullptr, d.T, false);
   for (uint32_t j = hdr_first ? j0 + 16u * G : j0; j < ngroups; j += 16u * G) {
     u32x4 h[kSpecHdrBytes / 16];
     if (j == j0) {
@@ -3606,7 +3550,7 @@ __global__ __launch_bounds__(1024) void spec_verify_kernel(SpecArgs a) {
   __syncthreads();
   stamp(3);
   // diagnostic build: every tile this workgroup verified of a published run
-  // counted, and the count is the prologue's restatement of what it owns
+  // counted, and the count is what the prologue's static_owned() said it owns
   // (an owned count too low would publish a run before its last tiles)
   if (kDiag && BATCH && wv == 0 && lane < nruns && ecnt[49] && ecnt[16u + lane] != kEarlyOff)
     (void)DCHK(ecnt[lane] == ecnt[16u + lane], kDkSpecEarly);

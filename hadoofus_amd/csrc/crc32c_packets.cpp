@@ -852,7 +852,7 @@ int spec_launch(DevCtx &c, SpecSlot &S, hipStream_t st, const uint8_t *d, uint64
   a.exc = S.exc;
   a.parity = uint32_t(S.n & 1u);
   a.seq = L.seq;
-  a.tune = tile_tune() | (g_spec_pool_min << 16);
+  a.tune = tile_tune(g_spec_pool_min);
   a.hout = S.hd;
   a.tabs = S.tabs;
   a.stamps = kDiag ? g_diag : nullptr;

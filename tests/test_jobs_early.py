@@ -77,7 +77,7 @@ def _run_held(engine, diag, streams, order):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("xcd,gshift", [(1, 3), (0, 3), (2, 3), (1, 0), (1, 4)])
+@pytest.mark.parametrize("xcd,gshift", [(1, 3), (0, 3), (2, 3), (1, 0), (1, 4), (2, 0), (0, 4)])
 def test_gpu_jobs_per_run_dealings(engine, oracle, xcd, gshift):
     """Six blocks in one batch, bad chunks at the last tile of block 1 and at
     the first tile of block 4, under each tile dealing: every job the
