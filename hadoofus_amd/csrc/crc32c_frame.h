@@ -21,6 +21,30 @@
 // fields skipped, groups and wire types 6/7 rejected, truncation rejected,
 // every required field present, last occurrence wins, bool = any nonzero
 // varint payload bit.
+//
+// Encodings the suite pins (tests/packet_stream.py builds them; expected
+// decodes come from the construction, the tests' CPU restatement of the
+// reference and google.protobuf):
+//   accepted: fields in any order; a field repeated (last value wins);
+//     unknown fields of wire types 0, 1, 2, 5 anywhere, field numbers up to
+//     2^29 - 1 (5-byte tags); tags and lengths padded with continuation
+//     bytes up to 5 bytes; bools as varints of 1-10 bytes with the set bit in
+//     any byte; syncBlock present or absent; 6 + hlen = 63, 64, 65, 4 000 and
+//     65 541 (hlen 65 535), the known fields before or behind the padding.
+//   rejected (INVALID_PACKETHEADERPROTO, nothing consumed): a required field
+//     missing; a known field number in another wire type (protobuf-c's rule;
+//     google.protobuf keeps it as unknown); group tags and wire types 6, 7;
+//     a one-byte tag of field number 0; the message ending inside a tag, a
+//     varint, a fixed32/64 or a length-delimited field; a tag still
+//     continuing after 5 bytes, a varint after 10.
+//   tests/test_header_decode.py runs 5 000 random ones through the host walk;
+//   tests/test_gpu_header_decode.py runs the accepted kinds through every
+//   device copy of this function (frame_build_kernel and small_run_kernel on
+//   the LDS window and on flat loads, the host walk over header windows and
+//   its D2H copy of long headers, spec_verify_kernel's prologue and its
+//   framing of a packet off the prediction), copy-out and jobs included.
+//   Not pinned: a field number 0 behind a padded tag (0x80 0x00), and length
+//   varints longer than 5 bytes -- decoders differ there.
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -31,27 +31,11 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, HERE)
 sys.path.insert(0, os.path.join(HERE, "..", "tests"))
 from oracle import Oracle, Reference, have_reference  # noqa: E402
-from packet_stream import CSUM_CRC32, CSUM_CRC32C, CSUM_NULL, header_v2, payload  # noqa: E402
+from packet_stream import (CSUM_CRC32, CSUM_CRC32C, CSUM_NULL, WT_VARINT, header_class,  # noqa: E402
+                           header_v2, header_v2_padded, header_v2_variant, payload, pb_tag)
 
 OUT = os.path.join(HERE, "..", "tests", "golden", "packet_cases.json")
 ERR_PROTO, ERR_SIZE, ERR_CRC_LEN, ERR_UNEXP_CRC, ERR_BAD = 18, 25, 26, 27, 29
-
-
-def header_class():
-    from google.protobuf import descriptor_pb2, descriptor_pool, message_factory
-    fdp = descriptor_pb2.FileDescriptorProto(name="packet_header.proto", package="hadoop.hdfs", syntax="proto2")
-    m = fdp.message_type.add(name="PacketHeaderProto")
-    F = descriptor_pb2.FieldDescriptorProto
-    for name, num, typ, lab in [("offsetInBlock", 1, F.TYPE_SFIXED64, F.LABEL_REQUIRED),
-                                ("seqno", 2, F.TYPE_SFIXED64, F.LABEL_REQUIRED),
-                                ("lastPacketInBlock", 3, F.TYPE_BOOL, F.LABEL_REQUIRED),
-                                ("dataLen", 4, F.TYPE_SFIXED32, F.LABEL_REQUIRED),
-                                ("syncBlock", 5, F.TYPE_BOOL, F.LABEL_OPTIONAL)]:
-        m.field.add(name=name, number=num, type=typ, label=lab)
-    pool = descriptor_pool.DescriptorPool()
-    pool.Add(fdp)
-    return message_factory.GetMessageClass(pool.FindMessageTypeByName("hadoop.hdfs.PacketHeaderProto"))
-
 
 PH = header_class()
 
@@ -310,6 +294,63 @@ def main():
     clean_run(c, [65536] * 8, {5: (1,)})
     c.max_pkts = 3
     cases.append(c.result(3, c.pkts[3]["stream_off"]))
+
+    # more PacketHeaderProto encodings (appended: the cases above keep their
+    # bytes).  Valid ones: google.protobuf must read the fields the case
+    # says; rejected ones: google.protobuf must refuse them too.
+    def variant_run(name, note, mk, dlens, corrupt=None):
+        """mk(k, offset, seqno, last, dlen) -> (header bytes, sync or None)."""
+        c = Case(name, 2, 512, CSUM_CRC32C, crcf, note)
+        off = 0
+        for k, dl in enumerate(list(dlens) + [0]):
+            last = dl == 0
+            hdr, sync = mk(k, off, k, last, dl)
+            m = pb_parse(hdr)
+            assert m.IsInitialized() and (m.offsetInBlock, m.seqno, m.lastPacketInBlock, m.dataLen) == \
+                (off, k, last, dl) and m.HasField("syncBlock") == (sync is not None) and m.syncBlock == bool(sync)
+            assert hdr != header_v2(off, k, last, dl, sync)
+            c.packet(dl, k, off, last=last, hdr=hdr, sync=sync, corrupt=(corrupt or {}).get(k, ()))
+            off += dl
+        cases.append(c.result(len(dlens) + 1, end_of(c)))
+
+    variant_run("proto_reordered_ok", "fields 4,3,2,1 (25 B); packet 1 carries 5,4,3,2,1 with syncBlock (27 B)",
+                lambda k, o, s, l, d: (header_v2_variant(o, s, l, d, True if k == 1 else None,
+                                                         order=(5, 4, 3, 2, 1)), True if k == 1 else None),
+                [65536, 65536, 7000], {1: (2,), 2: (13,)})
+    variant_run("proto_repeated_last_wins", "packet k repeats field 1, 4, 3, 2: a wrong value first, the last one wins",
+                lambda k, o, s, l, d: (header_v2_variant(o, s, l, d, repeat=(1, 4, 3, 2)[k]), None),
+                [65536, 65536, 7000], {1: (127,)})
+    variant_run("proto_padded_tags_ok", "every tag padded with 1, 2, 4 (5-byte tags) and 3 continuation bytes",
+                lambda k, o, s, l, d: (header_v2_variant(o, s, l, d, False, tag_pad=(1, 2, 4, 3)[k]), False),
+                [65536, 65536, 7000], {0: (0,)})
+    variant_run("proto_long_bool_ok", "bools as varints of 10, 2, 5 and 10 bytes; syncBlock true in packets 0 and 2",
+                lambda k, o, s, l, d: (header_v2_variant(o, s, l, d, k % 2 == 0, bool_bytes=(10, 2, 5, 10)[k]),
+                                       k % 2 == 0),
+                [65536, 65536, 7000], {2: (5,)})
+    variant_run("proto_header_65B_ok", "unknown bytes field 6 first: 6 + hlen = 65, CRCs and data behind it",
+                lambda k, o, s, l, d: (header_v2_padded(65, o, s, l, d), None),
+                [65536, 65536, 7000], {0: (1,), 2: (0, 13)})
+
+    def rejected_run(name, note, hdr):
+        try:
+            pb_parse(hdr)
+            raise AssertionError("google.protobuf accepts " + hdr.hex())
+        except Exception as e:  # google.protobuf.message.DecodeError
+            assert type(e).__name__ == "DecodeError", e
+        c = Case(name, 2, 512, CSUM_CRC32C, crcf, note)
+        c.packet(65536, 0, 0, corrupt=(7,))
+        consumed = c.pos
+        c.packet(65536, 1, 0, hdr=hdr, data=False, crc_override=b"",
+                 expect={"error": ERR_PROTO, "offset_in_block": 0, "seqno": 0, "data_len": 0, "crc_len": 0,
+                         "last": 0, "sync": 0})
+        cases.append(c.result(2, consumed))
+
+    ok = header_v2(65536, 1, False, 65536)
+    rejected_run("err_proto_truncated_varint", "the header ends inside syncBlock's varint", ok + b"\x28\x80")
+    rejected_run("err_proto_group", "a start-group tag (field 6, wire type 3) after the known fields",
+                 ok + pb_tag(6, 3))
+    rejected_run("err_proto_field0", "a field number 0 varint between seqno and lastPacketInBlock",
+                 ok[:18] + pb_tag(0, WT_VARINT) + b"\x01" + ok[18:])
 
     with open(OUT, "w") as f:
         json.dump({"generator": "oracle/gen_golden_packets.py", "zlib": zlib.ZLIB_RUNTIME_VERSION,
