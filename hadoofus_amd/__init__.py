@@ -7,6 +7,9 @@ and no fallback: if the library or a gfx950 device is missing, calls fail.
 Tuning knobs live only in the separate diagnostic build (tools/diaglib.py).
 The MD5CRC block / file checksums (include/hadoofus_md5crc.h) live in the
 companion library libhadoofus_md5crc.so, loaded on first use (md5crc.py).
+Gather writes (include/hadoofus_writev.h: a write's packets composed from a
+list of device buffers) live in libhadoofus_writev.so, loaded the same way
+(writev.py).
 """
 from .abi import (  # noqa: F401
     LIB_PATH, bind_product, bind_diag, CSUM_NULL, CSUM_CRC32, CSUM_CRC32C, ERR_BAD_CHECKSUM, ERR_CRC_LEN,
@@ -21,5 +24,6 @@ from .abi import (  # noqa: F401
 from .md5crc import (  # noqa: F401  (binds nothing until first use)
     FileChecksum, block_md5crcs, file_checksum, file_checksum_from_blocks, md5_host,
 )
+from .writev import compose_packets_iov, layout as writev_layout  # noqa: F401  (binds nothing until first use)
 
 __all__ = [n for n in dir() if not n.startswith("_")]

@@ -10,6 +10,11 @@ result-dropping store policies (include/hadoofus_crc32c_diag.h).  Only
 tools/ experiments and bench.py's ceiling measurement load it; the product
 library contains none of that code and reads no tuning knob from the
 environment.
+
+Two companion libraries link against the release library and are built after
+it: libhadoofus_md5crc.so (include/hadoofus_md5crc.h) and
+libhadoofus_writev.so (include/hadoofus_writev.h), each with its own sources
+and export map.
 """
 import os
 import subprocess
@@ -25,12 +30,16 @@ DIAG_LIB = os.path.join(LIBDIR, "libhadoofus_crc32c_diag.so")
 SOURCES = ["crc32c_kernels.hip", "crc32c_engine.cpp", "crc32c_packets.cpp"]
 DIAG_SOURCES = SOURCES + ["crc32c_probes.hip"]
 HEADERS = ["crc32c_internal.h", "crc32c_tables.h", "crc32c_packets.h", "crc32c_engine.h", "crc32c_frame.h",
-           "crc32c_hostpin.h", "crc32c_diag_ep.h", "crc32c_deal.h", "exports.map"]
+           "crc32c_hostpin.h", "crc32c_diag_ep.h", "crc32c_deal.h", "crc32c_outpkt.h", "exports.map"]
 PUBLIC = ["hadoofus_crc32c.h", "crc32c.h", "hadoofus_crc32c_diag.h"]
 MD5CRC_LIB = os.path.join(LIBDIR, "libhadoofus_md5crc.so")
 MD5CRC_SOURCES = ["md5crc_kernels.hip", "md5crc.cpp"]
 MD5CRC_HEADERS = ["md5_core.h", "md5crc_internal.h", "md5crc_exports.map"]
 MD5CRC_PUBLIC = ["hadoofus_md5crc.h", "hadoofus_crc32c.h"]
+WRITEV_LIB = os.path.join(LIBDIR, "libhadoofus_writev.so")
+WRITEV_SOURCES = ["writev_kernels.hip", "writev.cpp"]
+WRITEV_HEADERS = ["writev_internal.h", "crc32c_outpkt.h", "crc32c_tables.h", "writev_exports.map"]
+WRITEV_PUBLIC = ["hadoofus_writev.h", "hadoofus_crc32c.h"]
 ARCH = os.environ.get("HADOOFUS_OFFLOAD_ARCH", "gfx950")
 
 
@@ -61,17 +70,17 @@ def _cmd(out, sources, extra):
             f"-I{INCLUDE}", f"-I{CSRC}"] + extra + ["-o", out] + [os.path.join(CSRC, f) for f in sources]
 
 
-def _md5crc_cmd(out):
+def _companion_cmd(out, sources, exports):
     return [_hipcc(), f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC", "-shared", "-Wall",
-            "-Wno-unused-function", f"-Wl,--version-script={os.path.join(CSRC, 'md5crc_exports.map')}",
-            f"-I{INCLUDE}", f"-I{CSRC}", "-o", out] + [os.path.join(CSRC, f) for f in MD5CRC_SOURCES] + [
+            "-Wno-unused-function", f"-Wl,--version-script={os.path.join(CSRC, exports)}",
+            f"-I{INCLUDE}", f"-I{CSRC}", "-o", out] + [os.path.join(CSRC, f) for f in sources] + [
             f"-L{LIBDIR}", "-lhadoofus_crc32c", "-Wl,-rpath,$ORIGIN"]
 
 
 def build(force=False, verbose=False, diag=True):
     """Build the release library (and, with diag=True, the diagnostic one,
-    in parallel), then the MD5CRC companion.  Returns the release library's
-    path."""
+    in parallel), then the MD5CRC and gather-write companions (in parallel).
+    Returns the release library's path."""
     os.makedirs(LIBDIR, exist_ok=True)
     jobs = []
     if force or _stale(LIB, SOURCES):
@@ -87,13 +96,20 @@ def build(force=False, verbose=False, diag=True):
         if p.wait() != 0:
             raise subprocess.CalledProcessError(p.returncode, cmd)
         os.replace(out + ".tmp", out)
-    # the companion links against the release library, so after it is in place
-    if force or _stale(MD5CRC_LIB, MD5CRC_SOURCES, MD5CRC_HEADERS, MD5CRC_PUBLIC, [LIB]):
-        cmd = _md5crc_cmd(MD5CRC_LIB + ".tmp")
-        if verbose:
-            print(" ".join(cmd), file=sys.stderr)
-        subprocess.check_call(cmd)
-        os.replace(MD5CRC_LIB + ".tmp", MD5CRC_LIB)
+    # the companions link against the release library, so after it is in place
+    procs = []
+    for out, sources, headers, public, exports in (
+            (MD5CRC_LIB, MD5CRC_SOURCES, MD5CRC_HEADERS, MD5CRC_PUBLIC, "md5crc_exports.map"),
+            (WRITEV_LIB, WRITEV_SOURCES, WRITEV_HEADERS, WRITEV_PUBLIC, "writev_exports.map")):
+        if force or _stale(out, sources, headers, public, [LIB]):
+            cmd = _companion_cmd(out + ".tmp", sources, exports)
+            if verbose:
+                print(" ".join(cmd), file=sys.stderr)
+            procs.append((out, cmd, subprocess.Popen(cmd)))
+    for out, cmd, p in procs:
+        if p.wait() != 0:
+            raise subprocess.CalledProcessError(p.returncode, cmd)
+        os.replace(out + ".tmp", out)
     return LIB
 
 

@@ -1,0 +1,445 @@
+// libhadoofus_writev.so: entry points of include/hadoofus_writev.h.
+//
+// A companion of libhadoofus_crc32c.so, not a second engine: the device is
+// the one that library is bound to (hdfs_crc32c_init /
+// hdfs_crc32c_bound_device, its public API), the bulk of a gather write runs
+// as one compute plan of that library, and both share one HIP runtime.
+#include <hip/hip_runtime.h>
+
+#include <cstdarg>
+#include <cstdio>
+#include <cstring>
+#include <memory>
+#include <mutex>
+#include <vector>
+
+#include "crc32c_outpkt.h"
+#include "crc32c_tables.h"
+#include "hadoofus_writev.h"
+#include "writev_internal.h"
+
+namespace hdfs_writev {
+namespace {
+
+using namespace hdfs_crc32c::outpkt;
+
+// A run of whole chunks inside one fragment shorter than this is not worth a
+// segment-table entry: its chunks join the gathered set.  8 chunks are one
+// tile of the main library's tiled kernel; a shorter run would be a ragged
+// tile there, filled to less than its width, for the price of a table entry.
+constexpr uint32_t kMinSegChunks = 8;
+constexpr uint64_t kHostWindow = uint64_t(64) << 20;  // host fragments: bytes packed per call of the main library
+
+thread_local char g_err[512] = "";
+
+int fail(int code, const char *fmt, ...) {
+  va_list ap;
+  va_start(ap, fmt);
+  vsnprintf(g_err, sizeof(g_err), fmt, ap);
+  va_end(ap);
+  return code;
+}
+
+// A failure of the main library is this call's failure, with its text.
+int engine_fail(int rc, const char *what) { return fail(rc, "%s: %s", what, hdfs_crc32c_last_error()); }
+
+struct DeviceGuard {
+  int prev = -1;
+  bool changed = false;
+  explicit DeviceGuard(int dev) {
+    if (hipGetDevice(&prev) == hipSuccess && prev != dev) changed = hipSetDevice(dev) == hipSuccess;
+  }
+  ~DeviceGuard() {
+    if (changed) (void)hipSetDevice(prev);
+  }
+};
+
+// ---- layout -----------------------------------------------------------------
+// A run of whole chunks [chunk0, chunk0 + ...) inside fragment `frag`.
+struct Run {
+  int frag;
+  uint64_t at;      // byte offset of the run in the fragment
+  uint64_t len;     // bytes (the write's partial last chunk included)
+  uint64_t chunk0;  // first chunk: its place in the CRC array
+  uint64_t chunk1;  // one past the last
+};
+
+struct Layout {
+  hdfs_writev_layout_info info;
+  uint64_t n0 = 0;  // bytes of the short first chunk (0: the write starts on the grid)
+  std::vector<Run> runs;
+  std::vector<GChunk> chunks;  // filled only when bases are given
+  std::vector<Piece> pieces;
+};
+
+// The chunk grid is hdfs_crc32c_compose_packets': a short first chunk that
+// completes the block offset's chunk, then 512-B chunks, the last one possibly
+// partial.  bases == NULL: counts only.
+int build_layout(const uint64_t *lens, const void *const *bases, int n, int64_t off, Layout &L) {
+  L = Layout{};
+  hdfs_writev_layout_info &I = L.info;
+  std::memset(&I, 0, sizeof(I));
+  I.min_seg_chunks = kMinSegChunks;
+  uint64_t total = 0;
+  for (int f = 0; f < n; f++) {
+    if (lens[f] > (uint64_t(1) << 62) - total) return fail(HDFS_CRC32C_EINVAL, "fragment %d: the write's length overflows", f);
+    total += lens[f];
+  }
+  const uint64_t cs = kWriteChunk;
+  const uint64_t n0 = (total && off % int64_t(cs)) ? std::min<uint64_t>(total, cs - uint64_t(off % int64_t(cs))) : 0;
+  const uint64_t k0 = n0 ? 1 : 0;
+  const uint64_t nchunks = k0 + (total - n0 + cs - 1) / cs;
+  if (nchunks > 0xFFFFFFF0ull) return fail(HDFS_CRC32C_EINVAL, "more than 2^32 - 16 chunks in one write");
+  L.n0 = n0;
+  I.total = total;
+  I.nchunks = nchunks;
+  auto start = [&](uint64_t i) { return i < k0 ? 0 : n0 + (i - k0) * cs; };
+  auto end = [&](uint64_t i) { return std::min(start(i + 1), total); };
+  // runs of grid chunks wholly inside one fragment
+  uint64_t a = 0;
+  for (int f = 0; f < n; f++) {
+    if (!lens[f]) continue;
+    const uint64_t b = a + lens[f];
+    const uint64_t i0 = a <= n0 ? k0 : k0 + (a - n0 + cs - 1) / cs;               // first grid chunk starting at or after a
+    const uint64_t i1 = b == total ? nchunks : (b < n0 ? 0 : k0 + (b - n0) / cs);  // chunks ending at or before b
+    if (i1 > i0 && i1 - i0 >= kMinSegChunks) {
+      L.runs.push_back(Run{f, start(i0) - a, end(i1 - 1) - start(i0), i0, i1});
+      I.nsegments++;
+      I.seg_chunks += i1 - i0;
+    }
+    a = b;
+  }
+  // every other chunk is gathered from its pieces
+  I.ngathered = nchunks - I.seg_chunks;
+  if (bases) L.chunks.reserve(size_t(I.ngathered));
+  int f = 0;        // the first fragment that may reach into the chunk at hand
+  uint64_t fa = 0;  // its offset in the write
+  size_t ri = 0;
+  for (uint64_t i = 0; i < nchunks; i++) {
+    if (ri < L.runs.size() && i == L.runs[ri].chunk0) {
+      i = L.runs[ri++].chunk1 - 1;
+      continue;
+    }
+    const uint64_t s = start(i), e = end(i);
+    while (fa + lens[f] <= s) fa += lens[f++];  // s < total: ends inside the list
+    uint64_t pos = s, ga = fa;
+    uint32_t count = 0;
+    for (int g = f; pos < e; g++) {
+      const uint64_t ge = ga + lens[g];
+      if (ge > pos) {  // (a zero-length fragment has no piece)
+        const uint64_t take = std::min(e, ge) - pos;
+        if (bases) L.pieces.push_back(Piece{static_cast<const uint8_t *>(bases[g]) + (pos - ga), uint32_t(take), 0u});
+        pos += take;
+        count++;
+      }
+      ga = ge;
+    }
+    if (I.npieces + count > 0xFFFFFFF0ull) return fail(HDFS_CRC32C_EINVAL, "more than 2^32 - 16 pieces in one write");
+    if (bases) L.chunks.push_back(GChunk{uint32_t(i), uint32_t(I.npieces), count, 0u});
+    I.npieces += count;
+    I.max_pieces = std::max(I.max_pieces, count);
+  }
+  return HDFS_CRC32C_OK;
+}
+
+// ---- device scratch -----------------------------------------------------------
+// The CRC array, the chunk and piece tables and the pinned landing area of one
+// call, on the engine's device; grown on demand, never shrunk, kept between
+// calls.  Calls hold g_mu from the uploads to the final synchronise, so one
+// call's tables are never overwritten under its kernels.
+std::mutex g_mu;
+struct Scratch {
+  int dev = -1;
+  hipStream_t st = nullptr;
+  uint32_t *slice = nullptr;  // u32[2][kSliceWords]: CRC32C, CRC32
+  uint8_t *crc = nullptr, *tab = nullptr;
+  size_t crc_cap = 0, tab_cap = 0;
+  void *h_crc = nullptr;  // pinned (hdfs_crc32c_host_alloc)
+  size_t h_cap = 0;
+} g_s;
+
+void release_scratch() {
+  if (g_s.st) (void)hipStreamSynchronize(g_s.st);
+  if (g_s.slice) (void)hipFree(g_s.slice);
+  if (g_s.crc) (void)hipFree(g_s.crc);
+  if (g_s.tab) (void)hipFree(g_s.tab);
+  if (g_s.h_crc) (void)hdfs_crc32c_host_free(g_s.h_crc);
+  if (g_s.st) (void)hipStreamDestroy(g_s.st);
+  g_s = Scratch{};
+}
+
+int grow(uint8_t *&p, size_t &cap, size_t need) {
+  if (need <= cap) return HDFS_CRC32C_OK;
+  if (p) (void)hipFree(p);
+  p = nullptr;
+  cap = 0;
+  const size_t want = need < (64u << 10) ? (64u << 10) : need;
+  if (hipMalloc(&p, want) != hipSuccess) {
+    (void)hipGetLastError();
+    p = nullptr;
+    return fail(HDFS_CRC32C_ENOMEM, "device allocation of %zu bytes failed", want);
+  }
+  cap = want;
+  return HDFS_CRC32C_OK;
+}
+
+int reserve_scratch(int dev, size_t crc_bytes, size_t tab_bytes) {
+  if (g_s.dev != dev) {
+    if (g_s.dev >= 0) {
+      DeviceGuard g(g_s.dev);
+      release_scratch();
+    }
+    // a blocking stream: ordered after work queued earlier on the NULL stream
+    hipError_t e = hipStreamCreate(&g_s.st);
+    if (e == hipSuccess) e = hipMalloc(&g_s.slice, 2 * kSliceWords * sizeof(uint32_t));
+    if (e == hipSuccess) {
+      std::vector<uint32_t> t(2 * kSliceWords);
+      hdfs_crc32c::make_slicing4(reinterpret_cast<uint32_t(*)[256]>(t.data()), hdfs_crc32c::kPoly);
+      hdfs_crc32c::make_slicing4(reinterpret_cast<uint32_t(*)[256]>(t.data() + kSliceWords), hdfs_crc32c::kPolyZlib);
+      e = hipMemcpy(g_s.slice, t.data(), t.size() * sizeof(uint32_t), hipMemcpyHostToDevice);
+    }
+    if (e != hipSuccess) {
+      release_scratch();
+      return fail(HDFS_CRC32C_EHIP, "stream and tables: %s", hipGetErrorString(e));
+    }
+    g_s.dev = dev;
+  }
+  int rc;
+  if ((rc = grow(g_s.crc, g_s.crc_cap, crc_bytes)) || (rc = grow(g_s.tab, g_s.tab_cap, tab_bytes))) return rc;
+  if (crc_bytes > g_s.h_cap) {
+    if (g_s.h_crc) (void)hdfs_crc32c_host_free(g_s.h_crc);
+    g_s.h_crc = nullptr;
+    g_s.h_cap = 0;
+    const size_t want = crc_bytes < (64u << 10) ? (64u << 10) : crc_bytes;
+    if ((rc = hdfs_crc32c_host_alloc(&g_s.h_crc, want))) return engine_fail(rc, "pinned CRC landing area");
+    g_s.h_cap = want;
+  }
+  return HDFS_CRC32C_OK;
+}
+
+// ---- where the fragments live ---------------------------------------------------
+// All device memory of device `dev` (each inside one allocation) or all host
+// memory; zero-length fragments say nothing.
+int classify(const hdfs_crc32c_iovec *iov, int n, int dev, bool *on_device) {
+  uintptr_t lo = 0, hi = 0;  // the device allocation the last query found
+  int first = -1;
+  bool first_dev = false;
+  for (int i = 0; i < n; i++) {
+    if (!iov[i].len) continue;
+    const uintptr_t b = reinterpret_cast<uintptr_t>(iov[i].base);
+    bool d = false;
+    if (b >= lo && b < hi) {
+      d = true;
+    } else {
+      hipPointerAttribute_t a;
+      if (hipPointerGetAttributes(&a, iov[i].base) != hipSuccess) {
+        (void)hipGetLastError();  // memory the runtime does not know: host
+      } else if (a.type == hipMemoryTypeDevice) {
+        if (a.device != dev)
+          return fail(HDFS_CRC32C_EINVAL, "fragment %d: memory of device %d, the engine runs on device %d", i, a.device, dev);
+        void *ab = nullptr;
+        size_t as = 0;
+        if (hipMemGetAddressRange(&ab, &as, iov[i].base) != hipSuccess) {
+          (void)hipGetLastError();
+          return fail(HDFS_CRC32C_EINVAL, "fragment %d: no device allocation at %p", i, iov[i].base);
+        }
+        lo = reinterpret_cast<uintptr_t>(ab);
+        hi = lo + as;
+        d = true;
+      }
+    }
+    if (d && iov[i].len > hi - b)
+      return fail(HDFS_CRC32C_EINVAL, "fragment %d: %llu bytes at %p run past the end of its device allocation", i,
+                  (unsigned long long)iov[i].len, iov[i].base);
+    if (first < 0) {
+      first = i;
+      first_dev = d;
+    } else if (d != first_dev) {
+      return fail(HDFS_CRC32C_EINVAL, "fragment %d is %s memory, fragment %d is %s memory: mixed fragments", i,
+                  d ? "device" : "host", first, first_dev ? "device" : "host");
+    }
+  }
+  *on_device = first_dev;
+  return HDFS_CRC32C_OK;
+}
+
+// ---- device fragments -------------------------------------------------------------
+int compose_device(const hdfs_crc32c_iovec *iov, const Layout &L, int dev, const std::vector<OutPlan> &plan,
+                   int proto, int ctype, uint8_t *hdr_out, hdfs_crc32c_out_packet *pkts) {
+  const hdfs_writev_layout_info &I = L.info;
+  const size_t crc_bytes = size_t(I.nchunks) * 4;
+  const size_t ch_bytes = size_t(I.ngathered) * sizeof(GChunk), pc_bytes = size_t(I.npieces) * sizeof(Piece);
+  DeviceGuard g(dev);
+  std::lock_guard<std::mutex> lk(g_mu);
+  int rc = reserve_scratch(dev, crc_bytes, ch_bytes + pc_bytes);
+  if (rc) return rc;
+  uint32_t *d_crc = reinterpret_cast<uint32_t *>(g_s.crc);
+  GChunk *d_ch = reinterpret_cast<GChunk *>(g_s.tab);
+  Piece *d_pc = reinterpret_cast<Piece *>(g_s.tab + ch_bytes);
+  const bool zlib = ctype == HDFS_CRC32C_CSUM_CRC32;
+  // in place: every run is one segment of one compute plan, its CRCs at the
+  // run's place in the write's CRC array
+  hdfs_crc32c_plan *cplan = nullptr;
+  if (!L.runs.empty()) {
+    std::vector<hdfs_crc32c_segment> segs(L.runs.size());
+    for (size_t i = 0; i < segs.size(); i++) {
+      const Run &r = L.runs[i];
+      segs[i] = hdfs_crc32c_segment{static_cast<const uint8_t *>(iov[r.frag].base) + r.at, r.len, kWriteChunk,
+                                    HDFS_CRC32C_SEG_BE | (zlib ? HDFS_CRC32C_SEG_CRC32 : 0u), 0u, 0u,
+                                    d_crc + r.chunk0, nullptr};
+    }
+    if ((rc = hdfs_crc32c_plan_create(&cplan, HDFS_CRC32C_MODE_COMPUTE, segs.data(), segs.size())))
+      return engine_fail(rc, "compute plan");
+  }
+  hipStream_t st = g_s.st;
+  hipError_t e = hipSuccess;
+  if (ch_bytes) e = hipMemcpyAsync(d_ch, L.chunks.data(), ch_bytes, hipMemcpyHostToDevice, st);
+  if (e == hipSuccess && pc_bytes) e = hipMemcpyAsync(d_pc, L.pieces.data(), pc_bytes, hipMemcpyHostToDevice, st);
+  if (e == hipSuccess && cplan && (rc = hdfs_crc32c_plan_execute(cplan, st))) rc = engine_fail(rc, "compute plan");
+  if (e == hipSuccess && !rc)
+    e = launch_gather_chunks(d_ch, uint32_t(I.ngathered), d_pc, uint32_t(I.npieces), g_s.slice + (zlib ? kSliceWords : 0),
+                             d_crc, uint32_t(I.nchunks), st);
+  if (e == hipSuccess && !rc) e = hipMemcpyAsync(g_s.h_crc, d_crc, crc_bytes, hipMemcpyDeviceToHost, st);
+  // always: the tables and the CRC array must be out of use before the lock goes
+  const hipError_t se = hipStreamSynchronize(st);
+  if (e == hipSuccess) e = se;
+  if (cplan) hdfs_crc32c_plan_destroy(cplan);
+  if (rc) return rc;
+  if (e != hipSuccess) return fail(HDFS_CRC32C_EHIP, "gather write: %s", hipGetErrorString(e));
+  const uint32_t *crcs = static_cast<const uint32_t *>(g_s.h_crc);
+  write_out_packets(plan, proto, true, L.n0, crcs, crcs + (L.n0 ? 1 : 0), hdr_out, pkts);
+  return HDFS_CRC32C_OK;
+}
+
+// ---- host fragments ------------------------------------------------------------------
+// Packed window by window (whole packets of the write's plan, at most
+// kHostWindow bytes) into one host buffer; hdfs_crc32c_compose_packets does
+// each window at its running block offset and sequence number.
+int compose_host(const hdfs_crc32c_iovec *iov, uint64_t total, int64_t off, int64_t seq, int proto, int ctype,
+                 bool finish, uint8_t *hdr_out, uint64_t hdr_cap, hdfs_crc32c_out_packet *pkts, size_t max_pkts) {
+  std::vector<OutPlan> plan;
+  plan_out_packets(total, off, seq, false, plan);
+  std::unique_ptr<uint8_t[]> win(new uint8_t[size_t(std::min(total, kHostWindow))]);
+  int f = 0;        // fragment cursor
+  uint64_t fo = 0;  // bytes of fragment f already packed
+  uint64_t hpos = 0;
+  size_t np = 0;
+  for (size_t i = 0; i < plan.size();) {
+    size_t j = i;
+    uint64_t wlen = 0;
+    while (j < plan.size() && wlen + uint64_t(plan[j].dlen) <= kHostWindow) wlen += uint64_t(plan[j++].dlen);
+    for (uint64_t got = 0; got < wlen;) {
+      const uint64_t take = std::min(wlen - got, iov[f].len - fo);
+      if (take) std::memcpy(win.get() + got, static_cast<const uint8_t *>(iov[f].base) + fo, size_t(take));
+      got += take;
+      fo += take;
+      if (fo == iov[f].len && got < wlen) {
+        f++;
+        fo = 0;
+      }
+    }
+    size_t wn = 0;
+    uint64_t wused = 0;
+    const int rc = hdfs_crc32c_compose_packets(win.get(), wlen, plan[i].offset, plan[i].seqno, proto, ctype,
+                                               finish && j == plan.size() ? 1 : 0, hdr_out + hpos, hdr_cap - hpos,
+                                               pkts + np, max_pkts - np, &wn, &wused);
+    if (rc) return engine_fail(rc, "compose_packets");
+    for (size_t k = np; k < np + wn; k++) {
+      pkts[k].hdr_off += hpos;
+      pkts[k].data_off += plan[i].data_off;
+    }
+    np += wn;
+    hpos += wused;
+    i = j;
+  }
+  return HDFS_CRC32C_OK;
+}
+
+bool args_ok(int proto, int ctype, int64_t offset_in_block) {
+  if (proto != HDFS_CRC32C_PROTO_V1 && proto != HDFS_CRC32C_PROTO_V2) return fail(HDFS_CRC32C_EINVAL, "proto must be 1 or 2"), false;
+  if (ctype != HDFS_CRC32C_CSUM_NULL && ctype != HDFS_CRC32C_CSUM_CRC32 && ctype != HDFS_CRC32C_CSUM_CRC32C)
+    return fail(HDFS_CRC32C_EINVAL, "bad checksum type %d", ctype), false;
+  if (offset_in_block < 0) return fail(HDFS_CRC32C_EINVAL, "negative block offset"), false;
+  return true;
+}
+
+}  // namespace
+}  // namespace hdfs_writev
+
+using namespace hdfs_writev;
+
+extern "C" {
+
+int hdfs_writev_abi_version(void) { return HDFS_WRITEV_ABI_VERSION; }
+
+const char *hdfs_writev_last_error(void) { return g_err; }
+
+int hdfs_writev_layout(const uint64_t *lens, int iovcnt, int64_t offset_in_block, hdfs_writev_layout_info *out) {
+  if (!out) return fail(HDFS_CRC32C_EINVAL, "null out");
+  if (iovcnt < 0 || (iovcnt && !lens)) return fail(HDFS_CRC32C_EINVAL, "null or negative fragment list");
+  if (offset_in_block < 0) return fail(HDFS_CRC32C_EINVAL, "negative block offset");
+  Layout L;
+  const int rc = build_layout(lens, nullptr, iovcnt, offset_in_block, L);
+  if (rc) return rc;
+  *out = L.info;
+  return HDFS_CRC32C_OK;
+}
+
+int hdfs_writev_compose_packets(const hdfs_crc32c_iovec *iov, int iovcnt, int64_t offset_in_block, int64_t seqno,
+                                int proto, int ctype, int finish, void *hdr_out, uint64_t hdr_cap,
+                                hdfs_crc32c_out_packet *pkts, size_t max_pkts, size_t *npkts, uint64_t *hdr_used) {
+  if (npkts) *npkts = 0;
+  if (hdr_used) *hdr_used = 0;
+  if (iovcnt < 0) return fail(HDFS_CRC32C_EINVAL, "negative fragment count %d", iovcnt);
+  if (iovcnt && !iov) return fail(HDFS_CRC32C_EINVAL, "null fragment list");
+  if (!args_ok(proto, ctype, offset_in_block)) return HDFS_CRC32C_EINVAL;
+  uint64_t total = 0;
+  for (int i = 0; i < iovcnt; i++) {
+    if (iov[i].len && !iov[i].base) return fail(HDFS_CRC32C_EINVAL, "fragment %d: null base with %llu bytes", i,
+                                                (unsigned long long)iov[i].len);
+    if (iov[i].len > (uint64_t(1) << 62) - total) return fail(HDFS_CRC32C_EINVAL, "fragment %d: the write's length overflows", i);
+    total += iov[i].len;
+  }
+  int rc;
+  const bool csum = ctype != HDFS_CRC32C_CSUM_NULL;
+  std::vector<OutPlan> plan;
+  plan_out_packets(total, offset_in_block, seqno, finish != 0, plan);
+  const uint64_t need = out_plan_bytes(plan, proto, csum);
+  if (npkts) *npkts = plan.size();
+  if (hdr_used) *hdr_used = need;
+  if (!hdr_out || !pkts) return HDFS_CRC32C_OK;  // size query
+  if (max_pkts < plan.size() || hdr_cap < need)
+    return fail(HDFS_CRC32C_EINVAL, "need %zu packets / %llu header bytes", plan.size(), (unsigned long long)need);
+  uint8_t *out = static_cast<uint8_t *>(hdr_out);
+  if (!csum || !total) {  // sizing and headers only
+    write_out_packets(plan, proto, false, 0, nullptr, nullptr, out, pkts);
+    return HDFS_CRC32C_OK;
+  }
+  if (iovcnt == 1) {
+    rc = hdfs_crc32c_compose_packets(iov[0].base, iov[0].len, offset_in_block, seqno, proto, ctype, finish, hdr_out,
+                                     hdr_cap, pkts, max_pkts, npkts, hdr_used);
+    return rc ? engine_fail(rc, "compose_packets") : rc;
+  }
+  int dev = -1;
+  rc = hdfs_crc32c_init(-1);
+  if (rc == HDFS_CRC32C_OK) rc = hdfs_crc32c_bound_device(&dev, nullptr, 0);
+  if (rc) return engine_fail(rc, "engine");
+  bool on_device = false;
+  {
+    DeviceGuard g(dev);
+    if ((rc = classify(iov, iovcnt, dev, &on_device))) return rc;
+  }
+  if (!on_device)
+    return compose_host(iov, total, offset_in_block, seqno, proto, ctype, finish != 0, out, hdr_cap, pkts, max_pkts);
+  std::vector<uint64_t> lens(static_cast<size_t>(iovcnt));
+  std::vector<const void *> bases(static_cast<size_t>(iovcnt));
+  for (int i = 0; i < iovcnt; i++) {
+    lens[i] = iov[i].len;
+    bases[i] = iov[i].base;
+  }
+  Layout L;
+  if ((rc = build_layout(lens.data(), bases.data(), iovcnt, offset_in_block, L))) return rc;
+  return compose_device(iov, L, dev, plan, proto, ctype, out, pkts);
+}
+
+}  // extern "C"
