@@ -9,7 +9,9 @@ The MD5CRC block / file checksums (include/hadoofus_md5crc.h) live in the
 companion library libhadoofus_md5crc.so, loaded on first use (md5crc.py).
 Gather writes (include/hadoofus_writev.h: a write's packets composed from a
 list of device buffers) live in libhadoofus_writev.so, loaded the same way
-(writev.py).
+(writev.py).  A write's packets as one wire stream in device memory
+(include/hadoofus_wire.h: what verify_packets / read_packets consume) live in
+libhadoofus_wire.so, loaded the same way (wire.py).
 """
 from .abi import (  # noqa: F401
     LIB_PATH, bind_product, bind_diag, CSUM_NULL, CSUM_CRC32, CSUM_CRC32C, ERR_BAD_CHECKSUM, ERR_CRC_LEN,
@@ -25,5 +27,6 @@ from .md5crc import (  # noqa: F401  (binds nothing until first use)
     FileChecksum, block_md5crcs, file_checksum, file_checksum_from_blocks, md5_host,
 )
 from .writev import compose_packets_iov, layout as writev_layout  # noqa: F401  (binds nothing until first use)
+from .wire import compose_wire, layout as wire_layout  # noqa: F401  (binds nothing until first use)
 
 __all__ = [n for n in dir() if not n.startswith("_")]

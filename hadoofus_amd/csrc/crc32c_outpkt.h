@@ -2,7 +2,8 @@
 // (_send_packet / _compose_data_packet_header).  One definition, shared by
 // hdfs_crc32c_compose_packets (crc32c_packets.cpp) and the gather-write
 // companion library (writev.cpp): both write byte-identical header buffers.
-// Host code only.
+// Host code, except the byte writers marked HDFS_OUTPKT_HD: the wire-stream
+// companion's kernel (wire_kernels.hip) writes a packet's header with them.
 #ifndef HADOOFUS_CRC32C_OUTPKT_H
 #define HADOOFUS_CRC32C_OUTPKT_H
 
@@ -12,6 +13,12 @@
 #include <vector>
 
 #include "hadoofus_crc32c.h"
+
+#if defined(__HIPCC__)
+#define HDFS_OUTPKT_HD __host__ __device__
+#else
+#define HDFS_OUTPKT_HD
+#endif
 
 namespace hdfs_crc32c {
 namespace outpkt {
@@ -43,11 +50,11 @@ inline void plan_out_packets(uint64_t len, int64_t off, int64_t seq, bool finish
   if (finish) v.push_back(OutPlan{off, seq, pos, 0, true});
 }
 
-inline uint8_t *put_be(uint8_t *p, uint64_t v, int n) {
+HDFS_OUTPKT_HD inline uint8_t *put_be(uint8_t *p, uint64_t v, int n) {
   for (int i = n - 1; i >= 0; i--) *p++ = uint8_t(v >> (8 * i));
   return p;
 }
-inline uint8_t *put_le(uint8_t *p, uint64_t v, int n) {
+HDFS_OUTPKT_HD inline uint8_t *put_le(uint8_t *p, uint64_t v, int n) {
   for (int i = 0; i < n; i++) *p++ = uint8_t(v >> (8 * i));
   return p;
 }
@@ -56,7 +63,7 @@ inline uint8_t *put_le(uint8_t *p, uint64_t v, int n) {
 // (src/datanode.c:2795-2806): required fields in number order, sfixed64 /
 // sfixed32 little-endian, the bool as a one-byte varint, syncBlock unset.
 constexpr uint32_t kHdrProtoBytes = 25;
-inline uint8_t *put_header_proto(uint8_t *p, int64_t off, int64_t seq, bool last, int32_t dlen) {
+HDFS_OUTPKT_HD inline uint8_t *put_header_proto(uint8_t *p, int64_t off, int64_t seq, bool last, int32_t dlen) {
   *p++ = 0x09;  // field 1, wire type 1 (64-bit)
   p = put_le(p, uint64_t(off), 8);
   *p++ = 0x11;  // field 2, wire type 1
@@ -67,7 +74,23 @@ inline uint8_t *put_header_proto(uint8_t *p, int64_t off, int64_t seq, bool last
   return put_le(p, uint32_t(dlen), 4);
 }
 
-inline uint32_t out_header_bytes(int proto) { return proto == HDFS_CRC32C_PROTO_V1 ? 25u : 4u + 2u + kHdrProtoBytes; }
+HDFS_OUTPKT_HD inline uint32_t out_header_bytes(int proto) { return proto == HDFS_CRC32C_PROTO_V1 ? 25u : 4u + 2u + kHdrProtoBytes; }
+
+// One packet's header bytes alone -- plen, then hlen + PacketHeaderProto (v2)
+// or the v1 header -- as write_out_packets writes them ahead of the packet's
+// ncrc chunk CRCs: out_header_bytes(proto) bytes at p.
+HDFS_OUTPKT_HD inline uint8_t *put_out_header(uint8_t *p, int proto, int64_t off, int64_t seq, bool last,
+                                              int32_t dlen, uint64_t ncrc) {
+  p = put_be(p, uint64_t(uint32_t(int32_t(dlen + 4 * ncrc + 4))), 4);  // plen (src/datanode.c:2792)
+  if (proto == HDFS_CRC32C_PROTO_V2) {
+    p = put_be(p, kHdrProtoBytes, 2);  // hlen (s16)
+    return put_header_proto(p, off, seq, last, dlen);
+  }
+  p = put_be(p, uint64_t(off), 8);  // src/datanode.c:2808-2812
+  p = put_be(p, uint64_t(seq), 8);
+  *p++ = last ? 1 : 0;
+  return put_be(p, uint32_t(dlen), 4);
+}
 
 // Header bytes the plan's packets need (csum: 4 CRC bytes per chunk).
 inline uint64_t out_plan_bytes(const std::vector<OutPlan> &plan, int proto, bool csum) {

@@ -1,0 +1,324 @@
+// libhadoofus_wire.so: entry points of include/hadoofus_wire.h.
+//
+// A companion of libhadoofus_crc32c.so, not a second engine: the device is
+// the one that library is bound to (hdfs_crc32c_init /
+// hdfs_crc32c_bound_device, its public API), the chunk CRCs of a write come
+// from one compute plan of that library, and both share one HIP runtime.
+// This library's own kernel (frame_packets_kernel) only moves bytes.
+#include <hip/hip_runtime.h>
+
+#include <cstdarg>
+#include <cstdio>
+#include <cstring>
+#include <mutex>
+#include <vector>
+
+#include "crc32c_outpkt.h"
+#include "hadoofus_wire.h"
+#include "wire_internal.h"
+
+namespace hdfs_wire {
+namespace {
+
+using namespace hdfs_crc32c::outpkt;
+
+static_assert(kChunk == kWriteChunk && int64_t(kPacket) == kPacketSize, "one packet geometry");
+
+// Workgroups per packet and the store policy of the 16-B stores, as measured
+// (tools/wire_bench.py): plain stores beat write-through
+// ones at every size, and four workgroups per packet are fastest or within
+// 4 % of the fastest from 1 MiB to 1 GiB.
+constexpr uint32_t kSlices = 4;
+constexpr bool kSc1Stores = false;
+
+thread_local char g_err[512] = "";
+
+int fail(int code, const char *fmt, ...) {
+  va_list ap;
+  va_start(ap, fmt);
+  vsnprintf(g_err, sizeof(g_err), fmt, ap);
+  va_end(ap);
+  return code;
+}
+
+// A failure of the main library is this call's failure, with its text.
+int engine_fail(int rc, const char *what) { return fail(rc, "%s: %s", what, hdfs_crc32c_last_error()); }
+
+struct DeviceGuard {
+  int prev = -1;
+  bool changed = false;
+  explicit DeviceGuard(int dev) {
+    if (hipGetDevice(&prev) == hipSuccess && prev != dev) changed = hipSetDevice(dev) == hipSuccess;
+  }
+  ~DeviceGuard() {
+    if (changed) (void)hipSetDevice(prev);
+  }
+};
+
+// ---- layout -------------------------------------------------------------------
+struct Layout {
+  Write w;  // pointers not set
+  uint64_t nchunks = 0, wire_len = 0;
+  std::vector<OutPlan> plan;
+};
+
+bool args_ok(int proto, int ctype, int64_t offset_in_block, uint64_t len) {
+  if (proto != HDFS_CRC32C_PROTO_V1 && proto != HDFS_CRC32C_PROTO_V2) return fail(HDFS_CRC32C_EINVAL, "proto must be 1 or 2"), false;
+  if (ctype != HDFS_CRC32C_CSUM_NULL && ctype != HDFS_CRC32C_CSUM_CRC32 && ctype != HDFS_CRC32C_CSUM_CRC32C)
+    return fail(HDFS_CRC32C_EINVAL, "bad checksum type %d", ctype), false;
+  if (offset_in_block < 0) return fail(HDFS_CRC32C_EINVAL, "negative block offset"), false;
+  if (len > (uint64_t(1) << 40)) return fail(HDFS_CRC32C_EINVAL, "more than 1 TiB in one write"), false;
+  return true;
+}
+
+// Packet sizing is outpkt::plan_out_packets', the definition; the kernel's
+// closed form (packet_at) is checked against it packet by packet.
+int build_layout(uint64_t len, int64_t off, int64_t seq, int proto, int ctype, bool finish, Layout &L) {
+  plan_out_packets(len, off, seq, finish, L.plan);
+  Write &w = L.w;
+  std::memset(&w, 0, sizeof(w));
+  w.len = len;
+  w.off = off;
+  w.seq = seq;
+  w.n0 = uint32_t(out_head_bytes(L.plan, len, off));
+  w.npk = uint32_t(L.plan.size());
+  w.hb = out_header_bytes(proto);
+  w.proto = uint32_t(proto);
+  w.csum = ctype != HDFS_CRC32C_CSUM_NULL ? 1u : 0u;
+  w.finish = finish ? 1u : 0u;
+  w.slices = kSlices;
+  const uint32_t k0 = w.n0 ? 1u : 0u;
+  L.nchunks = k0 + (len - w.n0 + kChunk - 1) / kChunk;
+  uint64_t pos = 0;
+  for (size_t i = 0; i < L.plan.size(); i++) {
+    const OutPlan &k = L.plan[i];
+    const Pkt p = packet_at(w, uint32_t(i));
+    const uint64_t cidx = i < k0 ? 0u : k0 + (k.data_off - w.n0) / kChunk;  // as write_out_packets finds its CRCs
+    if (p.wire_off != pos || p.data_off != k.data_off || p.off != k.offset || p.seq != k.seqno ||
+        int32_t(p.dlen) != k.dlen || (p.last != 0u) != k.last || (p.ncrc && p.cidx != cidx) ||
+        p.cidx + uint64_t(p.ncrc) > L.nchunks)
+      return fail(HDFS_CRC32C_EINVAL, "internal: packet %zu of the write is not where its index puts it", i);
+    pos += w.hb + 4u * p.ncrc + p.dlen;
+  }
+  L.wire_len = pos;
+  return HDFS_CRC32C_OK;
+}
+
+// The packet records: hdfs_crc32c_compose_packets', hdr_off counting in the stream.
+void fill_records(const Layout &L, hdfs_crc32c_out_packet *pkts) {
+  for (size_t i = 0; i < L.plan.size(); i++) {
+    const OutPlan &k = L.plan[i];
+    const Pkt p = packet_at(L.w, uint32_t(i));
+    hdfs_crc32c_out_packet &o = pkts[i];
+    std::memset(&o, 0, sizeof(o));
+    o.hdr_off = p.wire_off;
+    o.data_off = k.data_off;
+    o.offset_in_block = k.offset;
+    o.seqno = k.seqno;
+    o.data_len = k.dlen;
+    o.hdr_len = L.w.hb + 4u * p.ncrc;
+    o.crc_len = 4u * p.ncrc;
+    o.last = k.last ? 1 : 0;
+  }
+}
+
+// ---- device scratch -----------------------------------------------------------
+// The CRC array of one call, on the engine's device; grown on demand, never
+// shrunk, kept between calls.  Calls hold g_mu from the plan to the final
+// synchronise, so one call's CRCs are never overwritten under its kernel.
+std::mutex g_mu;
+struct Scratch {
+  int dev = -1;
+  hipStream_t st = nullptr;
+  uint32_t *crc = nullptr;
+  size_t crc_cap = 0;
+  hipEvent_t ev[2] = {nullptr, nullptr};
+} g_s;
+
+void release_scratch() {
+  if (g_s.st) (void)hipStreamSynchronize(g_s.st);
+  if (g_s.crc) (void)hipFree(g_s.crc);
+  for (hipEvent_t e : g_s.ev)
+    if (e) (void)hipEventDestroy(e);
+  if (g_s.st) (void)hipStreamDestroy(g_s.st);
+  g_s = Scratch{};
+}
+
+int reserve_scratch(int dev, size_t crc_bytes) {
+  if (g_s.dev != dev) {
+    if (g_s.dev >= 0) {
+      DeviceGuard g(g_s.dev);
+      release_scratch();
+    }
+    // a blocking stream: ordered after work queued earlier on the NULL stream
+    const hipError_t e = hipStreamCreate(&g_s.st);
+    if (e != hipSuccess) {
+      g_s.st = nullptr;
+      return fail(HDFS_CRC32C_EHIP, "stream: %s", hipGetErrorString(e));
+    }
+    g_s.dev = dev;
+  }
+  if (crc_bytes <= g_s.crc_cap) return HDFS_CRC32C_OK;
+  if (g_s.crc) (void)hipFree(g_s.crc);
+  g_s.crc = nullptr;
+  g_s.crc_cap = 0;
+  const size_t want = crc_bytes < (64u << 10) ? (64u << 10) : crc_bytes;
+  if (hipMalloc(&g_s.crc, want) != hipSuccess) {
+    (void)hipGetLastError();
+    g_s.crc = nullptr;
+    return fail(HDFS_CRC32C_ENOMEM, "device allocation of %zu bytes failed", want);
+  }
+  g_s.crc_cap = want;
+  return HDFS_CRC32C_OK;
+}
+
+// ---- where the buffers live -------------------------------------------------------
+// [p, p + n) inside one allocation of device `dev`.
+int device_range(const void *p, uint64_t n, int dev, const char *what) {
+  hipPointerAttribute_t a;
+  if (hipPointerGetAttributes(&a, p) != hipSuccess) {
+    (void)hipGetLastError();  // memory the runtime does not know: host
+    return fail(HDFS_CRC32C_EINVAL, "%s: %p is not device memory", what, p);
+  }
+  if (a.type != hipMemoryTypeDevice) return fail(HDFS_CRC32C_EINVAL, "%s: %p is not device memory", what, p);
+  if (a.device != dev)
+    return fail(HDFS_CRC32C_EINVAL, "%s: memory of device %d, the engine runs on device %d", what, a.device, dev);
+  void *ab = nullptr;
+  size_t as = 0;
+  if (hipMemGetAddressRange(&ab, &as, const_cast<void *>(p)) != hipSuccess) {
+    (void)hipGetLastError();
+    return fail(HDFS_CRC32C_EINVAL, "%s: no device allocation at %p", what, p);
+  }
+  const uintptr_t lo = reinterpret_cast<uintptr_t>(ab), b = reinterpret_cast<uintptr_t>(p);
+  if (b < lo || b - lo > as || n > as - (b - lo))
+    return fail(HDFS_CRC32C_EINVAL, "%s: %llu bytes at %p run past the end of their device allocation", what,
+                (unsigned long long)n, p);
+  return HDFS_CRC32C_OK;
+}
+
+// ---- the call -------------------------------------------------------------------------
+// iters == 0: the call of hdfs_wire_compose_packets.  iters > 0: the same,
+// then the frame kernel alone iters more times between two events
+// (hdfs_wire_frame_time).
+int compose(const void *data, uint64_t len, int64_t off, int64_t seq, int proto, int ctype, int finish, void *wire,
+            uint64_t wire_cap, hdfs_crc32c_out_packet *pkts, size_t max_pkts, size_t *npkts, uint64_t *wire_len,
+            void *stream, unsigned flags, int iters, double *ms_per_iter) {
+  if (npkts) *npkts = 0;
+  if (wire_len) *wire_len = 0;
+  if (!args_ok(proto, ctype, off, len)) return HDFS_CRC32C_EINVAL;
+  Layout L;
+  int rc = build_layout(len, off, seq, proto, ctype, finish != 0, L);
+  if (rc) return rc;
+  if (npkts) *npkts = L.plan.size();
+  if (wire_len) *wire_len = L.wire_len;
+  const bool fits = pkts && max_pkts >= L.plan.size();
+  if (!wire) {  // size query; the records are closed-form, so they are filled when they fit
+    if (fits) fill_records(L, pkts);
+    return HDFS_CRC32C_OK;
+  }
+  if (len && !data) return fail(HDFS_CRC32C_EINVAL, "null data with %llu bytes", (unsigned long long)len);
+  if ((pkts && !fits) || wire_cap < L.wire_len)
+    return fail(HDFS_CRC32C_EINVAL, "need %zu packets / %llu stream bytes", L.plan.size(), (unsigned long long)L.wire_len);
+  if (!L.wire_len) return HDFS_CRC32C_OK;  // an empty write without finish: no packet
+  Write w = L.w;
+  const unsigned sl = (flags >> 8) & 0xFFu;
+  if (sl > kMaxSlices) return fail(HDFS_CRC32C_EINVAL, "at most %u workgroups per packet", kMaxSlices);
+  if (sl) w.slices = sl;
+  const bool sc1 = iters ? (flags & HDFS_WIRE_TIME_SC1) != 0 : kSc1Stores;
+  int dev = -1;
+  rc = hdfs_crc32c_init(-1);
+  if (rc == HDFS_CRC32C_OK) rc = hdfs_crc32c_bound_device(&dev, nullptr, 0);
+  if (rc) return engine_fail(rc, "engine");
+  DeviceGuard g(dev);
+  if (len && (rc = device_range(data, len, dev, "data"))) return rc;
+  if ((rc = device_range(wire, L.wire_len, dev, "wire"))) return rc;
+  const uintptr_t a = reinterpret_cast<uintptr_t>(data), b = reinterpret_cast<uintptr_t>(wire);
+  if (len && a < b + L.wire_len && b < a + len) return fail(HDFS_CRC32C_EINVAL, "data and wire overlap");
+  const bool crcs = w.csum && len;
+  std::lock_guard<std::mutex> lk(g_mu);
+  if ((rc = reserve_scratch(dev, crcs ? size_t(L.nchunks) * 4 : 0))) return rc;
+  if (iters && !g_s.ev[0] &&
+      (hipEventCreate(&g_s.ev[0]) != hipSuccess || hipEventCreate(&g_s.ev[1]) != hipSuccess))
+    return fail(HDFS_CRC32C_EHIP, "events: %s", hipGetErrorString(hipGetLastError()));
+  w.data = static_cast<const uint8_t *>(data);
+  w.crc = g_s.crc;
+  w.wire = static_cast<uint8_t *>(wire);
+  // the CRCs: compose_packets' chunk grid as segments of one compute plan, the
+  // short first chunk and the 512-B grid behind it
+  hdfs_crc32c_plan *cplan = nullptr;
+  if (crcs) {
+    const uint32_t sf = HDFS_CRC32C_SEG_BE | (ctype == HDFS_CRC32C_CSUM_CRC32 ? HDFS_CRC32C_SEG_CRC32 : 0u);
+    hdfs_crc32c_segment segs[2];
+    size_t ns = 0;
+    if (w.n0) segs[ns++] = hdfs_crc32c_segment{w.data, w.n0, kChunk, sf, 0u, 0u, g_s.crc, nullptr};
+    if (len > w.n0) segs[ns++] = hdfs_crc32c_segment{w.data + w.n0, len - w.n0, kChunk, sf, 0u, 0u,
+                                                      g_s.crc + (w.n0 ? 1 : 0), nullptr};
+    if ((rc = hdfs_crc32c_plan_create(&cplan, HDFS_CRC32C_MODE_COMPUTE, segs, ns))) return engine_fail(rc, "compute plan");
+  }
+  hipStream_t st = stream ? static_cast<hipStream_t>(stream) : g_s.st;
+  hipError_t e = hipSuccess;
+  if (cplan && (rc = hdfs_crc32c_plan_execute(cplan, st))) rc = engine_fail(rc, "compute plan");
+  if (!rc) e = launch_frame_packets(w, sc1, st);
+  if (!rc && e == hipSuccess && iters) {
+    e = hipEventRecord(g_s.ev[0], st);
+    for (int i = 0; i < iters && e == hipSuccess; i++) e = launch_frame_packets(w, sc1, st);
+    if (e == hipSuccess) e = hipEventRecord(g_s.ev[1], st);
+  }
+  // always: the CRC array must be out of use before the lock goes
+  const hipError_t se = hipStreamSynchronize(st);
+  if (e == hipSuccess) e = se;
+  if (cplan) hdfs_crc32c_plan_destroy(cplan);
+  if (rc) return rc;
+  if (e == hipSuccess && iters) {
+    float ms = 0;
+    e = hipEventElapsedTime(&ms, g_s.ev[0], g_s.ev[1]);
+    if (ms_per_iter) *ms_per_iter = double(ms) / iters;
+  }
+  if (e != hipSuccess) return fail(HDFS_CRC32C_EHIP, "wire stream: %s", hipGetErrorString(e));
+  if (fits) fill_records(L, pkts);
+  return HDFS_CRC32C_OK;
+}
+
+}  // namespace
+}  // namespace hdfs_wire
+
+using namespace hdfs_wire;
+
+extern "C" {
+
+int hdfs_wire_abi_version(void) { return HDFS_WIRE_ABI_VERSION; }
+
+const char *hdfs_wire_last_error(void) { return g_err; }
+
+int hdfs_wire_layout(uint64_t len, int64_t offset_in_block, int proto, int ctype, int finish,
+                     hdfs_wire_layout_info *out) {
+  if (!out) return fail(HDFS_CRC32C_EINVAL, "null out");
+  if (!args_ok(proto, ctype, offset_in_block, len)) return HDFS_CRC32C_EINVAL;
+  Layout L;
+  const int rc = build_layout(len, offset_in_block, 0, proto, ctype, finish != 0, L);
+  if (rc) return rc;
+  std::memset(out, 0, sizeof(*out));
+  out->npkts = L.plan.size();
+  out->nchunks = L.nchunks;
+  out->wire_len = L.wire_len;
+  out->packet_stride = L.w.hb + (L.w.csum ? 4u * (kPacket / kChunk) : 0u) + kPacket;
+  out->header_bytes = L.w.hb;
+  out->head_bytes = L.w.n0;
+  return HDFS_CRC32C_OK;
+}
+
+int hdfs_wire_compose_packets(const void *data, uint64_t len, int64_t offset_in_block, int64_t seqno, int proto,
+                              int ctype, int finish, void *wire, uint64_t wire_cap, hdfs_crc32c_out_packet *pkts,
+                              size_t max_pkts, size_t *npkts, uint64_t *wire_len, void *stream) {
+  return compose(data, len, offset_in_block, seqno, proto, ctype, finish, wire, wire_cap, pkts, max_pkts, npkts,
+                 wire_len, stream, 0u, 0, nullptr);
+}
+
+int hdfs_wire_frame_time(const void *data, uint64_t len, int64_t offset_in_block, int proto, int ctype, int finish,
+                         void *wire, uint64_t wire_cap, unsigned flags, int iters, double *ms_per_iter) {
+  if (iters < 1 || !ms_per_iter || !wire) return fail(HDFS_CRC32C_EINVAL, "iters >= 1, a stream buffer and ms_per_iter are needed");
+  return compose(data, len, offset_in_block, 0, proto, ctype, finish, wire, wire_cap, nullptr, 0, nullptr, nullptr,
+                 nullptr, flags, iters, ms_per_iter);
+}
+
+}  // extern "C"
