@@ -11,10 +11,13 @@ tools/ experiments and bench.py's ceiling measurement load it; the product
 library contains none of that code and reads no tuning knob from the
 environment.
 
-Three companion libraries link against the release library and are built
+Four companion libraries link against the release library and are built
 after it: libhadoofus_md5crc.so (include/hadoofus_md5crc.h),
-libhadoofus_writev.so (include/hadoofus_writev.h) and libhadoofus_wire.so
-(include/hadoofus_wire.h), each with its own sources and export map.
+libhadoofus_writev.so (include/hadoofus_writev.h), libhadoofus_wire.so
+(include/hadoofus_wire.h) and libhadoofus_wire_batch.so
+(include/hadoofus_wire_batch.h), each with its own sources and export map.
+The last two share the framing and layout code of wire_frame.h and
+wire_layout.h, compiled into both.
 """
 import os
 import subprocess
@@ -42,8 +45,13 @@ WRITEV_HEADERS = ["writev_internal.h", "crc32c_outpkt.h", "crc32c_tables.h", "wr
 WRITEV_PUBLIC = ["hadoofus_writev.h", "hadoofus_crc32c.h"]
 WIRE_LIB = os.path.join(LIBDIR, "libhadoofus_wire.so")
 WIRE_SOURCES = ["wire_kernels.hip", "wire.cpp"]
-WIRE_HEADERS = ["wire_internal.h", "crc32c_outpkt.h", "wire_exports.map"]
+WIRE_HEADERS = ["wire_internal.h", "wire_frame.h", "wire_layout.h", "crc32c_outpkt.h", "wire_exports.map"]
 WIRE_PUBLIC = ["hadoofus_wire.h", "hadoofus_crc32c.h"]
+WIRE_BATCH_LIB = os.path.join(LIBDIR, "libhadoofus_wire_batch.so")
+WIRE_BATCH_SOURCES = ["wire_batch_kernels.hip", "wire_batch.cpp"]
+WIRE_BATCH_HEADERS = ["wire_batch_internal.h", "wire_internal.h", "wire_frame.h", "wire_layout.h", "crc32c_outpkt.h",
+                      "wire_batch_exports.map"]
+WIRE_BATCH_PUBLIC = ["hadoofus_wire_batch.h", "hadoofus_crc32c.h"]
 ARCH = os.environ.get("HADOOFUS_OFFLOAD_ARCH", "gfx950")
 
 
@@ -83,8 +91,8 @@ def _companion_cmd(out, sources, exports):
 
 def build(force=False, verbose=False, diag=True):
     """Build the release library (and, with diag=True, the diagnostic one,
-    in parallel), then the MD5CRC, gather-write and wire-stream companions (in
-    parallel).
+    in parallel), then the MD5CRC, gather-write, wire-stream and wire-batch
+    companions (in parallel).
     Returns the release library's path."""
     os.makedirs(LIBDIR, exist_ok=True)
     jobs = []
@@ -106,7 +114,8 @@ def build(force=False, verbose=False, diag=True):
     for out, sources, headers, public, exports in (
             (MD5CRC_LIB, MD5CRC_SOURCES, MD5CRC_HEADERS, MD5CRC_PUBLIC, "md5crc_exports.map"),
             (WRITEV_LIB, WRITEV_SOURCES, WRITEV_HEADERS, WRITEV_PUBLIC, "writev_exports.map"),
-            (WIRE_LIB, WIRE_SOURCES, WIRE_HEADERS, WIRE_PUBLIC, "wire_exports.map")):
+            (WIRE_LIB, WIRE_SOURCES, WIRE_HEADERS, WIRE_PUBLIC, "wire_exports.map"),
+            (WIRE_BATCH_LIB, WIRE_BATCH_SOURCES, WIRE_BATCH_HEADERS, WIRE_BATCH_PUBLIC, "wire_batch_exports.map")):
         if force or _stale(out, sources, headers, public, [LIB]):
             cmd = _companion_cmd(out + ".tmp", sources, exports)
             if verbose:

@@ -1,0 +1,394 @@
+// libhadoofus_wire_batch.so: entry points of include/hadoofus_wire_batch.h.
+//
+// A companion of libhadoofus_crc32c.so, not a second engine: the device is
+// the one that library is bound to (hdfs_crc32c_init /
+// hdfs_crc32c_bound_device, its public API), the chunk CRCs of every write of
+// a batch come from one compute plan of that library, and both share one HIP
+// runtime.  The layout of a write and its records are wire_layout.h's, the
+// single-write library's own; this library's kernel (frame_batch_kernel) only
+// moves bytes, with wire_frame.h's code.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cstdarg>
+#include <cstdio>
+#include <cstring>
+#include <mutex>
+#include <vector>
+
+#include "crc32c_outpkt.h"
+#include "hadoofus_wire_batch.h"
+#include "wire_batch_internal.h"
+#include "wire_layout.h"
+
+namespace hdfs_wire {
+namespace {
+thread_local char g_err[512] = "";
+}  // namespace
+
+// This library's last-error text (wire_layout.h declares it for the shared
+// layout code).
+int fail(int code, const char *fmt, ...) {
+  va_list ap;
+  va_start(ap, fmt);
+  vsnprintf(g_err, sizeof(g_err), fmt, ap);
+  va_end(ap);
+  return code;
+}
+
+namespace {
+
+static_assert(kBatchSlices == kSlices, "the batch kernel deals a packet as frame_packets_kernel does");
+
+constexpr uint64_t kMaxPackets = 0x7FFFFFFFull / kBatchSlices;  // the grid: packets * 4 <= 2^31 - 1
+constexpr uint64_t kMaxChunks = 0xFFFFFFFFull - 15u;            // 2^32 - 16
+
+// The failure just recorded (by the shared layout code) was entry k's.
+int entry_fail(int rc, size_t k) {
+  char was[sizeof(g_err)];
+  std::memcpy(was, g_err, sizeof(was));
+  was[sizeof(was) - 1] = 0;
+  return fail(rc, "entry %zu: %s", k, was);
+}
+
+// A failure of the main library is this call's failure, with its text.
+int engine_fail(int rc, const char *what) { return fail(rc, "%s: %s", what, hdfs_crc32c_last_error()); }
+
+// ---- layout of the batch ------------------------------------------------------------
+struct Batch {
+  std::vector<Layout> L;  // per entry
+  uint64_t npkts = 0, nchunks = 0, wire_bytes = 0, entries = 0;
+};
+
+// Fills the out fields of every entry and the totals.
+int layout_batch(hdfs_wire_batch_write *w, size_t n, int proto, int ctype, Batch &B) {
+  if (n > HDFS_WIRE_BATCH_MAX_WRITES)
+    return fail(HDFS_CRC32C_EINVAL, "%zu writes, at most %d in one call", n, HDFS_WIRE_BATCH_MAX_WRITES);
+  if (n && !w) return fail(HDFS_CRC32C_EINVAL, "null writes");
+  for (size_t k = 0; k < n; k++) w[k].wire_len = w[k].npkts = w[k].first_pkt = 0;
+  // the arguments and the chunk total first, in closed form: a batch past the
+  // limit is refused before any write's packets are walked
+  uint64_t chunks = 0;
+  for (size_t k = 0; k < n; k++) {
+    if (!args_ok(proto, ctype, w[k].offset_in_block, w[k].len)) return entry_fail(HDFS_CRC32C_EINVAL, k);
+    const uint64_t mis = uint64_t(w[k].offset_in_block) % kChunk, to_grid = mis ? kChunk - mis : 0u;
+    const uint64_t n0 = std::min(w[k].len, to_grid);
+    chunks += (n0 ? 1u : 0u) + (w[k].len - n0 + kChunk - 1) / kChunk;  // <= 2^31 + 1 each, 65 536 of them
+  }
+  if (chunks > kMaxChunks)
+    return fail(HDFS_CRC32C_EINVAL, "%llu chunks in the batch, at most %llu", (unsigned long long)chunks,
+                (unsigned long long)kMaxChunks);
+  B.L.resize(n);
+  for (size_t k = 0; k < n; k++) {
+    Layout &L = B.L[k];
+    const int rc = build_layout(w[k].len, w[k].offset_in_block, w[k].seqno, proto, ctype, w[k].finish != 0, L);
+    if (rc) return entry_fail(rc, k);
+    w[k].wire_len = L.wire_len;
+    w[k].npkts = L.plan.size();
+    w[k].first_pkt = B.npkts;
+    B.npkts += L.plan.size();
+    B.nchunks += L.nchunks;
+    B.wire_bytes += L.wire_len;
+    B.entries += L.plan.empty() ? 0u : 1u;
+  }
+  // every entry's out fields are set before the totals are judged
+  if (B.npkts > kMaxPackets)
+    return fail(HDFS_CRC32C_EINVAL, "%llu packets in the batch, at most %llu", (unsigned long long)B.npkts,
+                (unsigned long long)kMaxPackets);
+  if (B.nchunks != chunks) return fail(HDFS_CRC32C_EINVAL, "internal: the batch's chunk counts do not add up");
+  return HDFS_CRC32C_OK;
+}
+
+void fill_batch_records(const hdfs_wire_batch_write *w, const Batch &B, hdfs_crc32c_out_packet *pkts) {
+  for (size_t k = 0; k < B.L.size(); k++) fill_records(B.L[k], pkts + w[k].first_pkt);
+}
+
+// ---- device scratch -----------------------------------------------------------
+// The CRC array, the device tables and their pinned staging area of one call,
+// on the engine's device; grown on demand, never shrunk, kept between calls.
+// Calls hold g_mu from the plan to the final synchronise, so one call's CRCs
+// and tables are never overwritten under its kernel.
+std::mutex g_mu;
+struct Scratch {
+  int dev = -1;
+  hipStream_t st = nullptr;
+  uint32_t *crc = nullptr;
+  size_t crc_cap = 0;
+  void *tab = nullptr, *pin = nullptr;
+  size_t tab_cap = 0;
+  hipEvent_t ev[2] = {nullptr, nullptr};
+} g_s;
+
+void release_scratch() {
+  if (g_s.st) (void)hipStreamSynchronize(g_s.st);
+  if (g_s.crc) (void)hipFree(g_s.crc);
+  if (g_s.tab) (void)hipFree(g_s.tab);
+  if (g_s.pin) (void)hipHostFree(g_s.pin);
+  for (hipEvent_t e : g_s.ev)
+    if (e) (void)hipEventDestroy(e);
+  if (g_s.st) (void)hipStreamDestroy(g_s.st);
+  g_s = Scratch{};
+}
+
+int reserve_scratch(int dev, size_t crc_bytes, size_t tab_bytes) {
+  if (g_s.dev != dev) {
+    if (g_s.dev >= 0) {
+      DeviceGuard g(g_s.dev);
+      release_scratch();
+    }
+    // a blocking stream: ordered after work queued earlier on the NULL stream
+    const hipError_t e = hipStreamCreate(&g_s.st);
+    if (e != hipSuccess) {
+      g_s.st = nullptr;
+      return fail(HDFS_CRC32C_EHIP, "stream: %s", hipGetErrorString(e));
+    }
+    g_s.dev = dev;
+  }
+  if (crc_bytes > g_s.crc_cap) {
+    if (g_s.crc) (void)hipFree(g_s.crc);
+    g_s.crc = nullptr;
+    g_s.crc_cap = 0;
+    const size_t want = crc_bytes < (64u << 10) ? (64u << 10) : crc_bytes;
+    if (hipMalloc(&g_s.crc, want) != hipSuccess) {
+      (void)hipGetLastError();
+      g_s.crc = nullptr;
+      return fail(HDFS_CRC32C_ENOMEM, "device allocation of %zu bytes failed", want);
+    }
+    g_s.crc_cap = want;
+  }
+  if (tab_bytes > g_s.tab_cap) {
+    if (g_s.tab) (void)hipFree(g_s.tab);
+    if (g_s.pin) (void)hipHostFree(g_s.pin);
+    g_s.tab = g_s.pin = nullptr;
+    g_s.tab_cap = 0;
+    const size_t want = tab_bytes < (16u << 10) ? (16u << 10) : tab_bytes;
+    if (hipMalloc(&g_s.tab, want) != hipSuccess || hipHostMalloc(&g_s.pin, want, hipHostMallocDefault) != hipSuccess) {
+      (void)hipGetLastError();
+      if (g_s.tab) (void)hipFree(g_s.tab);
+      g_s.tab = g_s.pin = nullptr;
+      return fail(HDFS_CRC32C_ENOMEM, "allocation of %zu table bytes failed", want);
+    }
+    g_s.tab_cap = want;
+  }
+  return HDFS_CRC32C_OK;
+}
+
+// ---- where the buffers live -------------------------------------------------------
+// device_range (wire_layout.h) asks the runtime about every pointer; the
+// ranges of a batch mostly share a few allocations, so the allocations found
+// so far answer first.
+struct Allocations {
+  struct A {
+    uintptr_t lo, hi;
+  };
+  std::vector<A> seen;
+  int check(const void *p, uint64_t n, int dev, const char *what) {
+    const uintptr_t b = reinterpret_cast<uintptr_t>(p);
+    for (const A &a : seen)
+      if (b >= a.lo && b < a.hi) {
+        if (n > a.hi - b)
+          return fail(HDFS_CRC32C_EINVAL, "%s: %llu bytes at %p run past the end of their device allocation", what,
+                      (unsigned long long)n, p);
+        return HDFS_CRC32C_OK;
+      }
+    A a{0, 0};
+    const int rc = device_range(p, n, dev, what, &a.lo, &a.hi);
+    if (rc == HDFS_CRC32C_OK && seen.size() < 64) seen.push_back(a);
+    return rc;
+  }
+};
+
+// No wire range overlaps another wire range or a data range: the intervals
+// sorted by their first byte, then one pass that remembers the furthest end
+// among the wire ranges and among the data ranges seen so far.
+struct Span {
+  uintptr_t lo, hi;  // [lo, hi), not empty
+  uint32_t k;        // entry
+  uint32_t wire;     // 1: a wire range
+};
+
+int check_overlaps(std::vector<Span> &v) {
+  std::sort(v.begin(), v.end(), [](const Span &a, const Span &b) {
+    return a.lo != b.lo ? a.lo < b.lo : (a.wire != b.wire ? a.wire > b.wire : a.k < b.k);
+  });
+  const Span *far_w = nullptr, *far_d = nullptr;
+  for (const Span &s : v) {
+    // every span ahead of s starts at or below s.lo: it overlaps s iff it ends behind s.lo
+    if (far_w && far_w->hi > s.lo) {
+      const uint32_t a = std::max(far_w->k, s.k), b = std::min(far_w->k, s.k);
+      return s.wire ? fail(HDFS_CRC32C_EINVAL, "entry %u: wire overlaps the wire of entry %u", a, b)
+                    : fail(HDFS_CRC32C_EINVAL, "entry %u: wire overlaps the data of entry %u", far_w->k, s.k);
+    }
+    if (s.wire && far_d && far_d->hi > s.lo)
+      return fail(HDFS_CRC32C_EINVAL, "entry %u: wire overlaps the data of entry %u", s.k, far_d->k);
+    const Span *&far = s.wire ? far_w : far_d;
+    if (!far || s.hi > far->hi) far = &s;
+  }
+  return HDFS_CRC32C_OK;
+}
+
+// ---- the call -------------------------------------------------------------------------
+// iters == 0: the call of hdfs_wire_batch_compose.  iters > 0: the same, then
+// the frame kernel alone iters more times between two events
+// (hdfs_wire_batch_frame_time).
+int compose(hdfs_wire_batch_write *w, size_t n, int proto, int ctype, hdfs_crc32c_out_packet *pkts, size_t max_pkts,
+            size_t *npkts, void *stream, int iters, double *ms_per_iter) {
+  if (npkts) *npkts = 0;
+  Batch B;
+  int rc = layout_batch(w, n, proto, ctype, B);
+  if (npkts) *npkts = size_t(B.npkts);
+  if (rc) return rc;
+  const bool fits = pkts && max_pkts >= B.npkts;
+  size_t with_wire = 0;
+  for (size_t k = 0; k < n; k++) with_wire += w[k].wire ? 1u : 0u;
+  if (!with_wire) {  // size query; the records are closed-form, so they are filled when they fit
+    if (fits) fill_batch_records(w, B, pkts);
+    return HDFS_CRC32C_OK;
+  }
+  if (with_wire != n) {
+    const bool first = w[0].wire != nullptr;
+    size_t k = 1;
+    while ((w[k].wire != nullptr) == first) k++;
+    return fail(HDFS_CRC32C_EINVAL, "entry %zu: wire is %s, entry 0's is not (every wire NULL is a size query)", k,
+                first ? "NULL" : "set");
+  }
+  for (size_t k = 0; k < n; k++) {
+    if (w[k].len && !w[k].data)
+      return fail(HDFS_CRC32C_EINVAL, "entry %zu: null data with %llu bytes", k, (unsigned long long)w[k].len);
+    if (w[k].wire_cap < w[k].wire_len)
+      return fail(HDFS_CRC32C_EINVAL, "entry %zu: %llu stream bytes, room for %llu", k,
+                  (unsigned long long)w[k].wire_len, (unsigned long long)w[k].wire_cap);
+    if (pkts && w[k].first_pkt + w[k].npkts > max_pkts)
+      return fail(HDFS_CRC32C_EINVAL, "entry %zu: its records end at %llu of %llu, room for %zu", k,
+                  (unsigned long long)(w[k].first_pkt + w[k].npkts), (unsigned long long)B.npkts, max_pkts);
+  }
+  if (!B.npkts) return HDFS_CRC32C_OK;  // nothing but empty writes without finish: no packet
+  int dev = -1;
+  rc = hdfs_crc32c_init(-1);
+  if (rc == HDFS_CRC32C_OK) rc = hdfs_crc32c_bound_device(&dev, nullptr, 0);
+  if (rc) return engine_fail(rc, "engine");
+  DeviceGuard g(dev);
+  {
+    Allocations al;
+    std::vector<Span> spans;
+    spans.reserve(2 * n);
+    for (size_t k = 0; k < n; k++) {
+      const uintptr_t a = reinterpret_cast<uintptr_t>(w[k].data), b = reinterpret_cast<uintptr_t>(w[k].wire);
+      if (w[k].len) {
+        if ((rc = al.check(w[k].data, w[k].len, dev, "data"))) return entry_fail(rc, k);
+        spans.push_back(Span{a, a + uintptr_t(w[k].len), uint32_t(k), 0u});
+      }
+      if (w[k].wire_len) {
+        if ((rc = al.check(w[k].wire, w[k].wire_len, dev, "wire"))) return entry_fail(rc, k);
+        spans.push_back(Span{b, b + uintptr_t(w[k].wire_len), uint32_t(k), 1u});
+      }
+    }
+    if ((rc = check_overlaps(spans))) return rc;
+  }
+  const bool crcs = ctype != HDFS_CRC32C_CSUM_NULL;
+  const uint32_t nw = uint32_t(B.entries), total = uint32_t(B.npkts);
+  const size_t tab_bytes = batch_table_bytes(nw);
+  std::lock_guard<std::mutex> lk(g_mu);
+  if ((rc = reserve_scratch(dev, crcs ? size_t(B.nchunks) * 4 : 0, tab_bytes))) return rc;
+  if (iters && !g_s.ev[0] &&
+      (hipEventCreate(&g_s.ev[0]) != hipSuccess || hipEventCreate(&g_s.ev[1]) != hipSuccess))
+    return fail(HDFS_CRC32C_EHIP, "events: %s", hipGetErrorString(hipGetLastError()));
+  // the tables, in pinned memory: the writes that have packets (the others are
+  // dropped here, so the kernel's search never meets an empty entry) and the
+  // prefix of their packet counts; the CRCs: every write's chunk grid as
+  // segments of one compute plan, the short first chunk and the 512-B grid
+  // behind it, write k's CRCs behind those of the writes ahead of it
+  Write *tab = static_cast<Write *>(g_s.pin);
+  uint32_t *pk0 = reinterpret_cast<uint32_t *>(tab + nw);
+  std::vector<hdfs_crc32c_segment> segs;
+  if (crcs) segs.reserve(2 * size_t(nw));
+  const uint32_t sf = HDFS_CRC32C_SEG_BE | (ctype == HDFS_CRC32C_CSUM_CRC32 ? HDFS_CRC32C_SEG_CRC32 : 0u);
+  uint64_t c0 = 0;
+  uint32_t e = 0;
+  for (size_t k = 0; k < n; k++) {
+    const Layout &L = B.L[k];
+    if (L.plan.empty()) continue;
+    Write &t = tab[e];
+    t = L.w;
+    t.slices = kBatchSlices;
+    t.data = static_cast<const uint8_t *>(w[k].data);
+    t.crc = g_s.crc + c0;
+    t.wire = static_cast<uint8_t *>(w[k].wire);
+    pk0[e++] = uint32_t(w[k].first_pkt);
+    if (crcs && t.len) {
+      if (t.n0) segs.push_back(hdfs_crc32c_segment{t.data, t.n0, kChunk, sf, 0u, 0u, g_s.crc + c0, nullptr});
+      if (t.len > t.n0)
+        segs.push_back(hdfs_crc32c_segment{t.data + t.n0, t.len - t.n0, kChunk, sf, 0u, 0u,
+                                           g_s.crc + c0 + (t.n0 ? 1 : 0), nullptr});
+      c0 += L.nchunks;
+    }
+  }
+  pk0[e] = total;
+  if (e != nw || c0 > B.nchunks) return fail(HDFS_CRC32C_EINVAL, "internal: the batch's tables do not add up");
+  hdfs_crc32c_plan *cplan = nullptr;
+  if (!segs.empty() && (rc = hdfs_crc32c_plan_create(&cplan, HDFS_CRC32C_MODE_COMPUTE, segs.data(), segs.size())))
+    return engine_fail(rc, "compute plan");
+  hipStream_t st = stream ? static_cast<hipStream_t>(stream) : g_s.st;
+  hipError_t he = hipMemcpyAsync(g_s.tab, g_s.pin, tab_bytes, hipMemcpyHostToDevice, st);
+  if (he == hipSuccess && cplan && (rc = hdfs_crc32c_plan_execute(cplan, st))) rc = engine_fail(rc, "compute plan");
+  if (!rc && he == hipSuccess) he = launch_frame_batch(g_s.tab, nw, total, st);
+  if (!rc && he == hipSuccess && iters) {
+    he = hipEventRecord(g_s.ev[0], st);
+    for (int i = 0; i < iters && he == hipSuccess; i++) he = launch_frame_batch(g_s.tab, nw, total, st);
+    if (he == hipSuccess) he = hipEventRecord(g_s.ev[1], st);
+  }
+  // always: the CRC array and the tables must be out of use before the lock goes
+  const hipError_t se = hipStreamSynchronize(st);
+  if (he == hipSuccess) he = se;
+  if (cplan) hdfs_crc32c_plan_destroy(cplan);
+  if (rc) return rc;
+  if (he == hipSuccess && iters) {
+    float ms = 0;
+    he = hipEventElapsedTime(&ms, g_s.ev[0], g_s.ev[1]);
+    if (ms_per_iter) *ms_per_iter = double(ms) / iters;
+  }
+  if (he != hipSuccess) return fail(HDFS_CRC32C_EHIP, "wire batch: %s", hipGetErrorString(he));
+  if (fits) fill_batch_records(w, B, pkts);
+  return HDFS_CRC32C_OK;
+}
+
+}  // namespace
+}  // namespace hdfs_wire
+
+using namespace hdfs_wire;
+
+extern "C" {
+
+int hdfs_wire_batch_abi_version(void) { return HDFS_WIRE_BATCH_ABI_VERSION; }
+
+const char *hdfs_wire_batch_last_error(void) { return g_err; }
+
+int hdfs_wire_batch_layout(hdfs_wire_batch_write *w, size_t nwrites, int proto, int ctype,
+                           hdfs_wire_batch_totals *out) {
+  if (!out) return fail(HDFS_CRC32C_EINVAL, "null out");
+  std::memset(out, 0, sizeof(*out));
+  Batch B;
+  const int rc = layout_batch(w, nwrites, proto, ctype, B);
+  out->npkts = B.npkts;
+  out->nchunks = B.nchunks;
+  out->wire_bytes = B.wire_bytes;
+  out->table_entries = B.entries;
+  return rc;
+}
+
+int hdfs_wire_batch_compose(hdfs_wire_batch_write *w, size_t nwrites, int proto, int ctype,
+                            hdfs_crc32c_out_packet *pkts, size_t max_pkts, size_t *npkts, void *stream) {
+  return compose(w, nwrites, proto, ctype, pkts, max_pkts, npkts, stream, 0, nullptr);
+}
+
+int hdfs_wire_batch_frame_time(hdfs_wire_batch_write *w, size_t nwrites, int proto, int ctype, int iters,
+                               double *ms_per_iter) {
+  if (iters < 1 || !ms_per_iter) return fail(HDFS_CRC32C_EINVAL, "iters >= 1 and ms_per_iter are needed");
+  *ms_per_iter = 0;
+  size_t with_wire = 0;
+  for (size_t k = 0; w && k < nwrites && k < HDFS_WIRE_BATCH_MAX_WRITES; k++) with_wire += w[k].wire ? 1u : 0u;
+  if (!with_wire) return fail(HDFS_CRC32C_EINVAL, "stream buffers are needed");
+  return compose(w, nwrites, proto, ctype, nullptr, 0, nullptr, nullptr, iters, ms_per_iter);
+}
+
+}  // extern "C"
