@@ -16,8 +16,11 @@ after it: libhadoofus_md5crc.so (include/hadoofus_md5crc.h),
 libhadoofus_writev.so (include/hadoofus_writev.h), libhadoofus_wire.so
 (include/hadoofus_wire.h) and libhadoofus_wire_batch.so
 (include/hadoofus_wire_batch.h), each with its own sources and export map.
-The last two share the framing and layout code of wire_frame.h and
-wire_layout.h, compiled into both.
+All four share the host support of companion_support.h (last error, the
+engine's device, grow-only buffers, scratch bound to a device, pointer
+placement, the end of a call); the last two also share the framing and layout
+code of wire_frame.h and wire_layout.h.  These headers are compiled into
+every library that includes them, each keeping its own copy.
 """
 import os
 import subprocess
@@ -37,20 +40,22 @@ HEADERS = ["crc32c_internal.h", "crc32c_tables.h", "crc32c_packets.h", "crc32c_e
 PUBLIC = ["hadoofus_crc32c.h", "crc32c.h", "hadoofus_crc32c_diag.h"]
 MD5CRC_LIB = os.path.join(LIBDIR, "libhadoofus_md5crc.so")
 MD5CRC_SOURCES = ["md5crc_kernels.hip", "md5crc.cpp"]
-MD5CRC_HEADERS = ["md5_core.h", "md5crc_internal.h", "md5crc_exports.map"]
+MD5CRC_HEADERS = ["md5_core.h", "md5crc_internal.h", "companion_support.h", "md5crc_exports.map"]
 MD5CRC_PUBLIC = ["hadoofus_md5crc.h", "hadoofus_crc32c.h"]
 WRITEV_LIB = os.path.join(LIBDIR, "libhadoofus_writev.so")
 WRITEV_SOURCES = ["writev_kernels.hip", "writev.cpp"]
-WRITEV_HEADERS = ["writev_internal.h", "crc32c_outpkt.h", "crc32c_tables.h", "writev_exports.map"]
+WRITEV_HEADERS = ["writev_internal.h", "crc32c_outpkt.h", "crc32c_tables.h", "companion_support.h",
+                  "writev_exports.map"]
 WRITEV_PUBLIC = ["hadoofus_writev.h", "hadoofus_crc32c.h"]
 WIRE_LIB = os.path.join(LIBDIR, "libhadoofus_wire.so")
 WIRE_SOURCES = ["wire_kernels.hip", "wire.cpp"]
-WIRE_HEADERS = ["wire_internal.h", "wire_frame.h", "wire_layout.h", "crc32c_outpkt.h", "wire_exports.map"]
+WIRE_HEADERS = ["wire_internal.h", "wire_frame.h", "wire_layout.h", "companion_support.h", "crc32c_outpkt.h",
+                "wire_exports.map"]
 WIRE_PUBLIC = ["hadoofus_wire.h", "hadoofus_crc32c.h"]
 WIRE_BATCH_LIB = os.path.join(LIBDIR, "libhadoofus_wire_batch.so")
 WIRE_BATCH_SOURCES = ["wire_batch_kernels.hip", "wire_batch.cpp"]
-WIRE_BATCH_HEADERS = ["wire_batch_internal.h", "wire_internal.h", "wire_frame.h", "wire_layout.h", "crc32c_outpkt.h",
-                      "wire_batch_exports.map"]
+WIRE_BATCH_HEADERS = ["wire_batch_internal.h", "wire_internal.h", "wire_frame.h", "wire_layout.h",
+                      "companion_support.h", "crc32c_outpkt.h", "wire_batch_exports.map"]
 WIRE_BATCH_PUBLIC = ["hadoofus_wire_batch.h", "hadoofus_crc32c.h"]
 ARCH = os.environ.get("HADOOFUS_OFFLOAD_ARCH", "gfx950")
 

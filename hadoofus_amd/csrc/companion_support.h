@@ -1,0 +1,262 @@
+// Host support shared by the companion libraries of libhadoofus_crc32c.so
+// (md5crc.cpp, writev.cpp, wire.cpp, wire_batch.cpp): the last-error text, the
+// engine's device, grow-only buffers, scratch bound to a device, where a
+// pointer lives, the packet argument check and the "always synchronise, then
+// report" tail of a call.  Host only: no kernel file includes it.  Every
+// library's export map keeps all of this local, so each library has its own
+// copy, its own last-error text included.
+#ifndef HADOOFUS_COMPANION_SUPPORT_H
+#define HADOOFUS_COMPANION_SUPPORT_H
+
+#include <hip/hip_runtime_api.h>
+
+#include <cstdarg>
+#include <cstdint>
+#include <cstdio>
+#include <cstring>
+
+#include "hadoofus_crc32c.h"
+
+namespace hdfs_companion {
+
+// ---- last error -----------------------------------------------------------------
+inline thread_local char g_err[512] = "";
+
+// Stores the calling thread's last-error text and returns code.
+__attribute__((format(printf, 2, 3))) inline int fail(int code, const char *fmt, ...) {
+  va_list ap;
+  va_start(ap, fmt);
+  vsnprintf(g_err, sizeof(g_err), fmt, ap);
+  va_end(ap);
+  return code;
+}
+
+inline const char *last_error() { return g_err; }
+
+// A failure of the main library is this call's failure, with its text.
+inline int engine_fail(int rc, const char *what) { return fail(rc, "%s: %s", what, hdfs_crc32c_last_error()); }
+
+// The failure just recorded gets a prefix ("entry 3", say): "<prefix>: <text>".
+__attribute__((format(printf, 2, 3))) inline int prefix_fail(int rc, const char *fmt, ...) {
+  char prefix[sizeof(g_err)], both[2 * sizeof(g_err) + 2];
+  va_list ap;
+  va_start(ap, fmt);
+  vsnprintf(prefix, sizeof(prefix), fmt, ap);
+  va_end(ap);
+  snprintf(both, sizeof(both), "%s: %s", prefix, g_err);
+  both[sizeof(g_err) - 1] = 0;  // cut at the end, as every text is
+  std::memcpy(g_err, both, sizeof(g_err));
+  return rc;
+}
+
+// ---- the engine's device --------------------------------------------------------
+struct DeviceGuard {
+  int prev = -1;
+  bool changed = false;
+  explicit DeviceGuard(int dev) {
+    if (hipGetDevice(&prev) == hipSuccess && prev != dev) changed = hipSetDevice(dev) == hipSuccess;
+  }
+  ~DeviceGuard() {
+    if (changed) (void)hipSetDevice(prev);
+  }
+  DeviceGuard(const DeviceGuard &) = delete;
+  DeviceGuard &operator=(const DeviceGuard &) = delete;
+};
+
+// The device the main library is bound to, initialising it if need be.
+inline int engine_device(int *dev) {
+  int rc = hdfs_crc32c_init(-1);
+  if (rc == HDFS_CRC32C_OK) rc = hdfs_crc32c_bound_device(dev, nullptr, 0);
+  return rc ? engine_fail(rc, "engine") : HDFS_CRC32C_OK;
+}
+
+// ---- grow-only buffers ------------------------------------------------------------
+// Grown on demand to max(bytes, floor), never shrunk, kept between calls; freed
+// means {null, 0}.  Alloc records the failure's text and returns its code.
+template <int (*Alloc)(void **, size_t), void (*Free)(void *)>
+struct GrowOnly {
+  void *p = nullptr;
+  size_t cap = 0;
+  int reserve(size_t bytes, size_t floor) {
+    if (bytes <= cap) return HDFS_CRC32C_OK;
+    release();
+    const size_t want = bytes < floor ? floor : bytes;
+    const int rc = Alloc(&p, want);
+    if (rc) {
+      p = nullptr;
+      return rc;
+    }
+    cap = want;
+    return HDFS_CRC32C_OK;
+  }
+  void release() {
+    if (p) Free(p);
+    p = nullptr;
+    cap = 0;
+  }
+  template <class T>
+  T *as() const {
+    return static_cast<T *>(p);
+  }
+};
+
+inline int device_alloc(void **p, size_t n) {
+  if (hipMalloc(p, n) == hipSuccess) return HDFS_CRC32C_OK;
+  (void)hipGetLastError();  // not sticky: the next call starts clean
+  return fail(HDFS_CRC32C_ENOMEM, "device allocation of %zu bytes failed", n);
+}
+inline void device_free(void *p) { (void)hipFree(p); }
+
+inline int pinned_alloc(void **p, size_t n) {
+  if (hipHostMalloc(p, n, hipHostMallocDefault) == hipSuccess) return HDFS_CRC32C_OK;
+  (void)hipGetLastError();
+  return fail(HDFS_CRC32C_ENOMEM, "pinned allocation of %zu bytes failed", n);
+}
+inline void pinned_free(void *p) { (void)hipHostFree(p); }
+
+using DeviceBuffer = GrowOnly<device_alloc, device_free>;
+// The pinned-host twin; the allocator is a parameter (writev.cpp's is the
+// engine's pin registry).
+template <int (*Alloc)(void **, size_t) = pinned_alloc, void (*Free)(void *) = pinned_free>
+using PinnedBuffer = GrowOnly<Alloc, Free>;
+
+constexpr size_t kScratchFloor = size_t(64) << 10;
+
+// ---- scratch bound to a device ------------------------------------------------------
+// The base of a library's scratch: the device it was built on and a blocking
+// stream of its own (ordered after work queued earlier on the NULL stream).
+// The library adds its buffers and says how to free them.
+struct DeviceScratch {
+  int dev = -1;
+  hipStream_t st = nullptr;
+
+  // Bound to device `to` (the current one) afterwards.  When it was bound to
+  // another device, everything is released there first.  `what` names the
+  // failure ("<what>: <the runtime's text>").
+  template <class ReleaseOwn>
+  int bind(int to, const char *what, ReleaseOwn &&release_own) {
+    if (dev == to) return HDFS_CRC32C_OK;
+    if (dev >= 0) {
+      DeviceGuard g(dev);
+      unbind(release_own);
+    }
+    const hipError_t e = hipStreamCreate(&st);
+    if (e != hipSuccess) {
+      st = nullptr;
+      return fail(HDFS_CRC32C_EHIP, "%s: %s", what, hipGetErrorString(e));
+    }
+    dev = to;
+    return HDFS_CRC32C_OK;
+  }
+
+  // Synchronise, free the library's buffers, then the stream: unbound.
+  template <class ReleaseOwn>
+  void unbind(ReleaseOwn &&release_own) {
+    if (st) (void)hipStreamSynchronize(st);
+    release_own();
+    if (st) (void)hipStreamDestroy(st);
+    st = nullptr;
+    dev = -1;
+  }
+};
+
+// ---- where a pointer lives ------------------------------------------------------------
+struct Placement {
+  enum Kind { kUnknown, kHost, kDevice };  // kUnknown: the runtime does not know the address
+  Kind kind = kUnknown;
+  int device = -1;
+  void *device_ptr = nullptr;  // NULL: no kernel can reach it
+  uintptr_t lo = 0, hi = 0;    // the allocation [lo, hi); 0, 0: not asked for or not found
+};
+
+// The allocation's range is asked for only where p is memory of device
+// range_on_dev (-1: never).
+inline Placement placement(const void *p, int range_on_dev = -1) {
+  Placement w;
+  hipPointerAttribute_t a;
+  if (hipPointerGetAttributes(&a, p) != hipSuccess) {
+    (void)hipGetLastError();
+    return w;
+  }
+  w.kind = a.type == hipMemoryTypeDevice ? Placement::kDevice : Placement::kHost;
+  w.device = a.device;
+  w.device_ptr = a.devicePointer;
+  if (w.kind == Placement::kDevice && a.device == range_on_dev) {
+    void *ab = nullptr;
+    size_t as = 0;
+    if (hipMemGetAddressRange(&ab, &as, const_cast<void *>(p)) != hipSuccess) {
+      (void)hipGetLastError();
+    } else {
+      w.lo = reinterpret_cast<uintptr_t>(ab);
+      w.hi = w.lo + as;
+    }
+  }
+  return w;
+}
+
+inline int past_the_end(const void *p, uint64_t n, const char *what) {
+  return fail(HDFS_CRC32C_EINVAL, "%s: %llu bytes at %p run past the end of their device allocation", what,
+              (unsigned long long)n, p);
+}
+
+// [p, p + n) inside one allocation of device `dev`.  alloc_lo / alloc_hi (may
+// be NULL): that allocation's address range, for a caller that checks many
+// ranges of one allocation.
+inline int device_range(const void *p, uint64_t n, int dev, const char *what, uintptr_t *alloc_lo = nullptr,
+                        uintptr_t *alloc_hi = nullptr) {
+  const Placement w = placement(p, dev);
+  if (w.kind != Placement::kDevice) return fail(HDFS_CRC32C_EINVAL, "%s: %p is not device memory", what, p);
+  if (w.device != dev)
+    return fail(HDFS_CRC32C_EINVAL, "%s: memory of device %d, the engine runs on device %d", what, w.device, dev);
+  if (!w.hi) return fail(HDFS_CRC32C_EINVAL, "%s: no device allocation at %p", what, p);
+  const uintptr_t b = reinterpret_cast<uintptr_t>(p);
+  if (b < w.lo || b > w.hi || n > w.hi - b) return past_the_end(p, n, what);
+  if (alloc_lo) *alloc_lo = w.lo;
+  if (alloc_hi) *alloc_hi = w.hi;
+  return HDFS_CRC32C_OK;
+}
+
+// device_range asks the runtime about every pointer; the ranges of a batch
+// mostly share a few allocations, so the allocations found so far answer first.
+struct Allocations {
+  struct A {
+    uintptr_t lo, hi;
+  };
+  A seen[64];
+  size_t nseen = 0;
+  int check(const void *p, uint64_t n, int dev, const char *what) {
+    const uintptr_t b = reinterpret_cast<uintptr_t>(p);
+    for (size_t i = 0; i < nseen; i++)
+      if (b >= seen[i].lo && b < seen[i].hi) return n > seen[i].hi - b ? past_the_end(p, n, what) : HDFS_CRC32C_OK;
+    A a{0, 0};
+    const int rc = device_range(p, n, dev, what, &a.lo, &a.hi);
+    if (rc == HDFS_CRC32C_OK && nseen < 64) seen[nseen++] = a;
+    return rc;
+  }
+};
+
+// ---- the arguments of a packet run -----------------------------------------------------
+inline bool packet_args_ok(int proto, int ctype, int64_t offset_in_block) {
+  if (proto != HDFS_CRC32C_PROTO_V1 && proto != HDFS_CRC32C_PROTO_V2) return fail(HDFS_CRC32C_EINVAL, "proto must be 1 or 2"), false;
+  if (ctype != HDFS_CRC32C_CSUM_NULL && ctype != HDFS_CRC32C_CSUM_CRC32 && ctype != HDFS_CRC32C_CSUM_CRC32C)
+    return fail(HDFS_CRC32C_EINVAL, "bad checksum type %d", ctype), false;
+  if (offset_in_block < 0) return fail(HDFS_CRC32C_EINVAL, "negative block offset"), false;
+  return true;
+}
+
+// ---- the end of a call -------------------------------------------------------------------
+// Always synchronises, even after an error: the scratch must be out of use
+// before the caller's lock goes.  Then the plan (may be NULL) is destroyed, and
+// the call's result is the engine's rc, else the HIP error as "<what>: <text>".
+inline int sync_and_report(hipStream_t st, hipError_t e, int rc, hdfs_crc32c_plan *plan, const char *what) {
+  const hipError_t se = hipStreamSynchronize(st);
+  if (e == hipSuccess) e = se;
+  if (plan) hdfs_crc32c_plan_destroy(plan);
+  if (rc) return rc;
+  if (e != hipSuccess) return fail(HDFS_CRC32C_EHIP, "%s: %s", what, hipGetErrorString(e));
+  return HDFS_CRC32C_OK;
+}
+
+}  // namespace hdfs_companion
+
+#endif  // HADOOFUS_COMPANION_SUPPORT_H

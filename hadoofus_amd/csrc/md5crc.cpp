@@ -5,12 +5,12 @@
 // hdfs_crc32c_bound_device, its public API), and both share one HIP runtime.
 #include <hip/hip_runtime.h>
 
-#include <cstdarg>
 #include <cstdio>
 #include <cstring>
 #include <mutex>
 #include <vector>
 
+#include "companion_support.h"
 #include "hadoofus_md5crc.h"
 #include "md5_core.h"
 #include "md5crc_internal.h"
@@ -18,70 +18,26 @@
 namespace hdfs_md5crc {
 namespace {
 
-thread_local char g_err[512] = "";
-
-int fail(int code, const char *fmt, ...) {
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(g_err, sizeof(g_err), fmt, ap);
-  va_end(ap);
-  return code;
-}
-
-#define MD5CRC_HIPCHK(expr)                                                                        \
-  do {                                                                                             \
-    hipError_t e_ = (expr);                                                                        \
-    if (e_ != hipSuccess) return fail(HDFS_CRC32C_EHIP, "%s: %s", #expr, hipGetErrorString(e_));   \
-  } while (0)
-
-struct DeviceGuard {
-  int prev = -1;
-  bool changed = false;
-  explicit DeviceGuard(int dev) {
-    if (hipGetDevice(&prev) == hipSuccess && prev != dev) changed = hipSetDevice(dev) == hipSuccess;
-  }
-  ~DeviceGuard() {
-    if (changed) (void)hipSetDevice(prev);
-  }
-};
+using namespace hdfs_companion;
 
 // The segment table and the digests of one call, on the engine's device;
 // grown on demand, kept between calls (an allocation per call would cost
-// more than the launch).  Calls hold g_mu from the upload to the final
+// more than the launch).  The calls run on the caller's stream, so this
+// scratch has none of its own.  Calls hold g_mu from the upload to the final
 // synchronise, so one call's table is never overwritten under its kernel.
 std::mutex g_mu;
-void *g_scratch = nullptr;
-size_t g_scratch_cap = 0;
+DeviceBuffer g_scratch;
 int g_scratch_dev = -1;
 
 int scratch(int dev, size_t bytes, void **out) {
-  if (g_scratch && (g_scratch_dev != dev || g_scratch_cap < bytes)) {
-    (void)hipFree(g_scratch);
-    g_scratch = nullptr;
-    g_scratch_cap = 0;
-  }
-  if (!g_scratch) {
-    const size_t cap = bytes < (64u << 10) ? (64u << 10) : bytes;
-    if (hipMalloc(&g_scratch, cap) != hipSuccess) {
-      (void)hipGetLastError();
-      g_scratch = nullptr;
-      return fail(HDFS_CRC32C_ENOMEM, "device allocation of %zu bytes failed", cap);
-    }
-    g_scratch_cap = cap;
-    g_scratch_dev = dev;
-  }
-  *out = g_scratch;
-  return HDFS_CRC32C_OK;
+  if (g_scratch_dev != dev) g_scratch.release();
+  g_scratch_dev = dev;
+  const int rc = g_scratch.reserve(bytes, kScratchFloor);
+  *out = g_scratch.p;
+  return rc;
 }
 
-bool device_accessible(const void *p) {
-  hipPointerAttribute_t a;
-  if (hipPointerGetAttributes(&a, p) != hipSuccess) {
-    (void)hipGetLastError();
-    return false;
-  }
-  return a.devicePointer != nullptr;
-}
+bool device_accessible(const void *p) { return placement(p).device_ptr != nullptr; }
 
 int seg_ctype(uint32_t flags) {
   return (flags & HDFS_CRC32C_SEG_CRC32) ? HDFS_CRC32C_CSUM_CRC32 : HDFS_CRC32C_CSUM_CRC32C;
@@ -147,7 +103,7 @@ extern "C" {
 
 int hdfs_md5crc_abi_version(void) { return HDFS_MD5CRC_ABI_VERSION; }
 
-const char *hdfs_md5crc_last_error(void) { return g_err; }
+const char *hdfs_md5crc_last_error(void) { return last_error(); }
 
 int hdfs_md5crc_md5_host(const void *buf, uint64_t len, void *out16) {
   if (!out16 || (len && !buf)) return fail(HDFS_CRC32C_EINVAL, "null buffer / out");
@@ -159,10 +115,9 @@ int hdfs_md5crc_block_digests(const hdfs_crc32c_segment *segs, size_t nseg, void
   if (!nseg) return HDFS_CRC32C_OK;
   if (!segs || !md5_out) return fail(HDFS_CRC32C_EINVAL, "null segments / md5_out");
   if (nseg > (size_t(1) << 26)) return fail(HDFS_CRC32C_EINVAL, "too many segments");
-  int rc = hdfs_crc32c_init(-1);
   int dev = -1;
-  if (rc == HDFS_CRC32C_OK) rc = hdfs_crc32c_bound_device(&dev, nullptr, 0);
-  if (rc) return fail(rc, "engine: %s", hdfs_crc32c_last_error());
+  int rc = engine_device(&dev);
+  if (rc) return rc;
   DeviceGuard g(dev);
   std::vector<SegTab> tab(nseg);
   for (size_t i = 0; i < nseg; i++) {
@@ -180,10 +135,7 @@ int hdfs_md5crc_block_digests(const hdfs_crc32c_segment *segs, size_t nseg, void
   if (e == hipSuccess) e = launch_block_digests(d_tab, uint32_t(nseg), d_out, st);
   if (e == hipSuccess) e = hipMemcpyAsync(md5_out, d_out, nseg * HDFS_MD5CRC_LEN, hipMemcpyDefault, st);
   // always: the table and the digests must be out of use before the lock goes
-  const hipError_t se = hipStreamSynchronize(st);
-  if (e == hipSuccess) e = se;
-  if (e != hipSuccess) return fail(HDFS_CRC32C_EHIP, "block digests: %s", hipGetErrorString(e));
-  return HDFS_CRC32C_OK;
+  return sync_and_report(st, e, HDFS_CRC32C_OK, nullptr, "block digests");
 }
 
 int hdfs_md5crc_file_from_blocks(const void *block_md5s, size_t nblocks, uint32_t bytes_per_crc,

@@ -7,11 +7,8 @@
 // This library's own kernel (frame_packets_kernel) only moves bytes.
 #include <hip/hip_runtime.h>
 
-#include <cstdarg>
-#include <cstdio>
 #include <cstring>
 #include <mutex>
-#include <vector>
 
 #include "crc32c_outpkt.h"
 #include "hadoofus_wire.h"
@@ -19,20 +16,6 @@
 #include "wire_layout.h"
 
 namespace hdfs_wire {
-namespace {
-thread_local char g_err[512] = "";
-}  // namespace
-
-// This library's last-error text (wire_layout.h declares it for the shared
-// layout code).
-int fail(int code, const char *fmt, ...) {
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(g_err, sizeof(g_err), fmt, ap);
-  va_end(ap);
-  return code;
-}
-
 namespace {
 
 using namespace hdfs_crc32c::outpkt;
@@ -42,62 +25,37 @@ using namespace hdfs_crc32c::outpkt;
 // Workgroups per packet: kSlices (wire_layout.h).
 constexpr bool kSc1Stores = false;
 
-// A failure of the main library is this call's failure, with its text.
-int engine_fail(int rc, const char *what) { return fail(rc, "%s: %s", what, hdfs_crc32c_last_error()); }
-
 // The layout of a write (Layout, args_ok, build_layout), its records
-// (fill_records) and the check of a buffer's place (device_range) are
-// wire_layout.h's, shared with the batch library.
+// (fill_records), its plan segments (grid_segments) and the frame run
+// (timed_frame_run) are wire_layout.h's, shared with the batch library; the
+// last-error text, the scratch base and the check of a buffer's place
+// (device_range) are companion_support.h's.
 
 // ---- device scratch -----------------------------------------------------------
 // The CRC array of one call, on the engine's device; grown on demand, never
 // shrunk, kept between calls.  Calls hold g_mu from the plan to the final
 // synchronise, so one call's CRCs are never overwritten under its kernel.
 std::mutex g_mu;
-struct Scratch {
-  int dev = -1;
-  hipStream_t st = nullptr;
-  uint32_t *crc = nullptr;
-  size_t crc_cap = 0;
-  hipEvent_t ev[2] = {nullptr, nullptr};
+struct Scratch : DeviceScratch {
+  DeviceBuffer crc;
+  hipEvent_t ev[2] = {nullptr, nullptr};  // of the timing call, created when it first runs
+
+  int reserve(int to, size_t crc_bytes) {
+    const int rc = bind(to, "stream", [this] {
+      crc.release();
+      for (hipEvent_t &e : ev) {
+        if (e) (void)hipEventDestroy(e);
+        e = nullptr;
+      }
+    });
+    return rc ? rc : crc.reserve(crc_bytes, kScratchFloor);
+  }
+  int timing_events() {
+    if (!ev[0] && (hipEventCreate(&ev[0]) != hipSuccess || hipEventCreate(&ev[1]) != hipSuccess))
+      return fail(HDFS_CRC32C_EHIP, "events: %s", hipGetErrorString(hipGetLastError()));
+    return HDFS_CRC32C_OK;
+  }
 } g_s;
-
-void release_scratch() {
-  if (g_s.st) (void)hipStreamSynchronize(g_s.st);
-  if (g_s.crc) (void)hipFree(g_s.crc);
-  for (hipEvent_t e : g_s.ev)
-    if (e) (void)hipEventDestroy(e);
-  if (g_s.st) (void)hipStreamDestroy(g_s.st);
-  g_s = Scratch{};
-}
-
-int reserve_scratch(int dev, size_t crc_bytes) {
-  if (g_s.dev != dev) {
-    if (g_s.dev >= 0) {
-      DeviceGuard g(g_s.dev);
-      release_scratch();
-    }
-    // a blocking stream: ordered after work queued earlier on the NULL stream
-    const hipError_t e = hipStreamCreate(&g_s.st);
-    if (e != hipSuccess) {
-      g_s.st = nullptr;
-      return fail(HDFS_CRC32C_EHIP, "stream: %s", hipGetErrorString(e));
-    }
-    g_s.dev = dev;
-  }
-  if (crc_bytes <= g_s.crc_cap) return HDFS_CRC32C_OK;
-  if (g_s.crc) (void)hipFree(g_s.crc);
-  g_s.crc = nullptr;
-  g_s.crc_cap = 0;
-  const size_t want = crc_bytes < (64u << 10) ? (64u << 10) : crc_bytes;
-  if (hipMalloc(&g_s.crc, want) != hipSuccess) {
-    (void)hipGetLastError();
-    g_s.crc = nullptr;
-    return fail(HDFS_CRC32C_ENOMEM, "device allocation of %zu bytes failed", want);
-  }
-  g_s.crc_cap = want;
-  return HDFS_CRC32C_OK;
-}
 
 // ---- the call -------------------------------------------------------------------------
 // iters == 0: the call of hdfs_wire_compose_packets.  iters > 0: the same,
@@ -129,9 +87,7 @@ int compose(const void *data, uint64_t len, int64_t off, int64_t seq, int proto,
   if (sl) w.slices = sl;
   const bool sc1 = iters ? (flags & HDFS_WIRE_TIME_SC1) != 0 : kSc1Stores;
   int dev = -1;
-  rc = hdfs_crc32c_init(-1);
-  if (rc == HDFS_CRC32C_OK) rc = hdfs_crc32c_bound_device(&dev, nullptr, 0);
-  if (rc) return engine_fail(rc, "engine");
+  if ((rc = engine_device(&dev))) return rc;
   DeviceGuard g(dev);
   if (len && (rc = device_range(data, len, dev, "data"))) return rc;
   if ((rc = device_range(wire, L.wire_len, dev, "wire"))) return rc;
@@ -139,45 +95,20 @@ int compose(const void *data, uint64_t len, int64_t off, int64_t seq, int proto,
   if (len && a < b + L.wire_len && b < a + len) return fail(HDFS_CRC32C_EINVAL, "data and wire overlap");
   const bool crcs = w.csum && len;
   std::lock_guard<std::mutex> lk(g_mu);
-  if ((rc = reserve_scratch(dev, crcs ? size_t(L.nchunks) * 4 : 0))) return rc;
-  if (iters && !g_s.ev[0] &&
-      (hipEventCreate(&g_s.ev[0]) != hipSuccess || hipEventCreate(&g_s.ev[1]) != hipSuccess))
-    return fail(HDFS_CRC32C_EHIP, "events: %s", hipGetErrorString(hipGetLastError()));
+  if ((rc = g_s.reserve(dev, crcs ? size_t(L.nchunks) * 4 : 0)) || (iters && (rc = g_s.timing_events()))) return rc;
   w.data = static_cast<const uint8_t *>(data);
-  w.crc = g_s.crc;
+  w.crc = g_s.crc.as<uint32_t>();
   w.wire = static_cast<uint8_t *>(wire);
-  // the CRCs: compose_packets' chunk grid as segments of one compute plan, the
-  // short first chunk and the 512-B grid behind it
+  // the CRCs: one compute plan over the write's chunk grid
   hdfs_crc32c_plan *cplan = nullptr;
-  if (crcs) {
-    const uint32_t sf = HDFS_CRC32C_SEG_BE | (ctype == HDFS_CRC32C_CSUM_CRC32 ? HDFS_CRC32C_SEG_CRC32 : 0u);
-    hdfs_crc32c_segment segs[2];
-    size_t ns = 0;
-    if (w.n0) segs[ns++] = hdfs_crc32c_segment{w.data, w.n0, kChunk, sf, 0u, 0u, g_s.crc, nullptr};
-    if (len > w.n0) segs[ns++] = hdfs_crc32c_segment{w.data + w.n0, len - w.n0, kChunk, sf, 0u, 0u,
-                                                      g_s.crc + (w.n0 ? 1 : 0), nullptr};
-    if ((rc = hdfs_crc32c_plan_create(&cplan, HDFS_CRC32C_MODE_COMPUTE, segs, ns))) return engine_fail(rc, "compute plan");
-  }
+  hdfs_crc32c_segment segs[2];
+  const size_t ns = grid_segments(w, g_s.crc.as<uint32_t>(), ctype, segs);
+  if (ns && (rc = hdfs_crc32c_plan_create(&cplan, HDFS_CRC32C_MODE_COMPUTE, segs, ns))) return engine_fail(rc, "compute plan");
   hipStream_t st = stream ? static_cast<hipStream_t>(stream) : g_s.st;
-  hipError_t e = hipSuccess;
-  if (cplan && (rc = hdfs_crc32c_plan_execute(cplan, st))) rc = engine_fail(rc, "compute plan");
-  if (!rc) e = launch_frame_packets(w, sc1, st);
-  if (!rc && e == hipSuccess && iters) {
-    e = hipEventRecord(g_s.ev[0], st);
-    for (int i = 0; i < iters && e == hipSuccess; i++) e = launch_frame_packets(w, sc1, st);
-    if (e == hipSuccess) e = hipEventRecord(g_s.ev[1], st);
-  }
-  // always: the CRC array must be out of use before the lock goes
-  const hipError_t se = hipStreamSynchronize(st);
-  if (e == hipSuccess) e = se;
-  if (cplan) hdfs_crc32c_plan_destroy(cplan);
+  // the CRC array is out of use when this returns, so before the lock goes
+  rc = timed_frame_run(st, hipSuccess, cplan, g_s.ev, iters, ms_per_iter, "wire stream",
+                       [&] { return launch_frame_packets(w, sc1, st); });
   if (rc) return rc;
-  if (e == hipSuccess && iters) {
-    float ms = 0;
-    e = hipEventElapsedTime(&ms, g_s.ev[0], g_s.ev[1]);
-    if (ms_per_iter) *ms_per_iter = double(ms) / iters;
-  }
-  if (e != hipSuccess) return fail(HDFS_CRC32C_EHIP, "wire stream: %s", hipGetErrorString(e));
   if (fits) fill_records(L, pkts);
   return HDFS_CRC32C_OK;
 }
@@ -191,7 +122,7 @@ extern "C" {
 
 int hdfs_wire_abi_version(void) { return HDFS_WIRE_ABI_VERSION; }
 
-const char *hdfs_wire_last_error(void) { return g_err; }
+const char *hdfs_wire_last_error(void) { return last_error(); }
 
 int hdfs_wire_layout(uint64_t len, int64_t offset_in_block, int proto, int ctype, int finish,
                      hdfs_wire_layout_info *out) {

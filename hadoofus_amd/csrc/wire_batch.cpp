@@ -10,8 +10,6 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <cstdarg>
-#include <cstdio>
 #include <cstring>
 #include <mutex>
 #include <vector>
@@ -23,36 +21,15 @@
 
 namespace hdfs_wire {
 namespace {
-thread_local char g_err[512] = "";
-}  // namespace
-
-// This library's last-error text (wire_layout.h declares it for the shared
-// layout code).
-int fail(int code, const char *fmt, ...) {
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(g_err, sizeof(g_err), fmt, ap);
-  va_end(ap);
-  return code;
-}
-
-namespace {
 
 static_assert(kBatchSlices == kSlices, "the batch kernel deals a packet as frame_packets_kernel does");
 
 constexpr uint64_t kMaxPackets = 0x7FFFFFFFull / kBatchSlices;  // the grid: packets * 4 <= 2^31 - 1
 constexpr uint64_t kMaxChunks = 0xFFFFFFFFull - 15u;            // 2^32 - 16
+constexpr size_t kTableFloor = size_t(16) << 10;
 
 // The failure just recorded (by the shared layout code) was entry k's.
-int entry_fail(int rc, size_t k) {
-  char was[sizeof(g_err)];
-  std::memcpy(was, g_err, sizeof(was));
-  was[sizeof(was) - 1] = 0;
-  return fail(rc, "entry %zu: %s", k, was);
-}
-
-// A failure of the main library is this call's failure, with its text.
-int engine_fail(int rc, const char *what) { return fail(rc, "%s: %s", what, hdfs_crc32c_last_error()); }
+int entry_fail(int rc, size_t k) { return prefix_fail(rc, "entry %zu", k); }
 
 // ---- layout of the batch ------------------------------------------------------------
 struct Batch {
@@ -109,95 +86,39 @@ void fill_batch_records(const hdfs_wire_batch_write *w, const Batch &B, hdfs_crc
 // Calls hold g_mu from the plan to the final synchronise, so one call's CRCs
 // and tables are never overwritten under its kernel.
 std::mutex g_mu;
-struct Scratch {
-  int dev = -1;
-  hipStream_t st = nullptr;
-  uint32_t *crc = nullptr;
-  size_t crc_cap = 0;
-  void *tab = nullptr, *pin = nullptr;
-  size_t tab_cap = 0;
-  hipEvent_t ev[2] = {nullptr, nullptr};
+struct Scratch : DeviceScratch {
+  DeviceBuffer crc, tab;
+  PinnedBuffer<> pin;                     // the tables' staging area: tab's twin, grown with it
+  hipEvent_t ev[2] = {nullptr, nullptr};  // of the timing call, created when it first runs
+
+  int reserve(int to, size_t crc_bytes, size_t tab_bytes) {
+    int rc = bind(to, "stream", [this] {
+      crc.release();
+      tab.release();
+      pin.release();
+      for (hipEvent_t &e : ev) {
+        if (e) (void)hipEventDestroy(e);
+        e = nullptr;
+      }
+    });
+    if (rc || (rc = crc.reserve(crc_bytes, kScratchFloor))) return rc;
+    if (tab_bytes <= tab.cap) return HDFS_CRC32C_OK;
+    tab.release();  // both go before either comes back
+    pin.release();
+    if (tab.reserve(tab_bytes, kTableFloor) || pin.reserve(tab_bytes, kTableFloor)) {
+      tab.release();
+      return fail(HDFS_CRC32C_ENOMEM, "allocation of %zu table bytes failed", std::max(tab_bytes, kTableFloor));
+    }
+    return HDFS_CRC32C_OK;
+  }
+  int timing_events() {
+    if (!ev[0] && (hipEventCreate(&ev[0]) != hipSuccess || hipEventCreate(&ev[1]) != hipSuccess))
+      return fail(HDFS_CRC32C_EHIP, "events: %s", hipGetErrorString(hipGetLastError()));
+    return HDFS_CRC32C_OK;
+  }
 } g_s;
 
-void release_scratch() {
-  if (g_s.st) (void)hipStreamSynchronize(g_s.st);
-  if (g_s.crc) (void)hipFree(g_s.crc);
-  if (g_s.tab) (void)hipFree(g_s.tab);
-  if (g_s.pin) (void)hipHostFree(g_s.pin);
-  for (hipEvent_t e : g_s.ev)
-    if (e) (void)hipEventDestroy(e);
-  if (g_s.st) (void)hipStreamDestroy(g_s.st);
-  g_s = Scratch{};
-}
-
-int reserve_scratch(int dev, size_t crc_bytes, size_t tab_bytes) {
-  if (g_s.dev != dev) {
-    if (g_s.dev >= 0) {
-      DeviceGuard g(g_s.dev);
-      release_scratch();
-    }
-    // a blocking stream: ordered after work queued earlier on the NULL stream
-    const hipError_t e = hipStreamCreate(&g_s.st);
-    if (e != hipSuccess) {
-      g_s.st = nullptr;
-      return fail(HDFS_CRC32C_EHIP, "stream: %s", hipGetErrorString(e));
-    }
-    g_s.dev = dev;
-  }
-  if (crc_bytes > g_s.crc_cap) {
-    if (g_s.crc) (void)hipFree(g_s.crc);
-    g_s.crc = nullptr;
-    g_s.crc_cap = 0;
-    const size_t want = crc_bytes < (64u << 10) ? (64u << 10) : crc_bytes;
-    if (hipMalloc(&g_s.crc, want) != hipSuccess) {
-      (void)hipGetLastError();
-      g_s.crc = nullptr;
-      return fail(HDFS_CRC32C_ENOMEM, "device allocation of %zu bytes failed", want);
-    }
-    g_s.crc_cap = want;
-  }
-  if (tab_bytes > g_s.tab_cap) {
-    if (g_s.tab) (void)hipFree(g_s.tab);
-    if (g_s.pin) (void)hipHostFree(g_s.pin);
-    g_s.tab = g_s.pin = nullptr;
-    g_s.tab_cap = 0;
-    const size_t want = tab_bytes < (16u << 10) ? (16u << 10) : tab_bytes;
-    if (hipMalloc(&g_s.tab, want) != hipSuccess || hipHostMalloc(&g_s.pin, want, hipHostMallocDefault) != hipSuccess) {
-      (void)hipGetLastError();
-      if (g_s.tab) (void)hipFree(g_s.tab);
-      g_s.tab = g_s.pin = nullptr;
-      return fail(HDFS_CRC32C_ENOMEM, "allocation of %zu table bytes failed", want);
-    }
-    g_s.tab_cap = want;
-  }
-  return HDFS_CRC32C_OK;
-}
-
 // ---- where the buffers live -------------------------------------------------------
-// device_range (wire_layout.h) asks the runtime about every pointer; the
-// ranges of a batch mostly share a few allocations, so the allocations found
-// so far answer first.
-struct Allocations {
-  struct A {
-    uintptr_t lo, hi;
-  };
-  std::vector<A> seen;
-  int check(const void *p, uint64_t n, int dev, const char *what) {
-    const uintptr_t b = reinterpret_cast<uintptr_t>(p);
-    for (const A &a : seen)
-      if (b >= a.lo && b < a.hi) {
-        if (n > a.hi - b)
-          return fail(HDFS_CRC32C_EINVAL, "%s: %llu bytes at %p run past the end of their device allocation", what,
-                      (unsigned long long)n, p);
-        return HDFS_CRC32C_OK;
-      }
-    A a{0, 0};
-    const int rc = device_range(p, n, dev, what, &a.lo, &a.hi);
-    if (rc == HDFS_CRC32C_OK && seen.size() < 64) seen.push_back(a);
-    return rc;
-  }
-};
-
 // No wire range overlaps another wire range or a data range: the intervals
 // sorted by their first byte, then one pass that remembers the furthest end
 // among the wire ranges and among the data ranges seen so far.
@@ -264,9 +185,7 @@ int compose(hdfs_wire_batch_write *w, size_t n, int proto, int ctype, hdfs_crc32
   }
   if (!B.npkts) return HDFS_CRC32C_OK;  // nothing but empty writes without finish: no packet
   int dev = -1;
-  rc = hdfs_crc32c_init(-1);
-  if (rc == HDFS_CRC32C_OK) rc = hdfs_crc32c_bound_device(&dev, nullptr, 0);
-  if (rc) return engine_fail(rc, "engine");
+  if ((rc = engine_device(&dev))) return rc;
   DeviceGuard g(dev);
   {
     Allocations al;
@@ -289,20 +208,18 @@ int compose(hdfs_wire_batch_write *w, size_t n, int proto, int ctype, hdfs_crc32
   const uint32_t nw = uint32_t(B.entries), total = uint32_t(B.npkts);
   const size_t tab_bytes = batch_table_bytes(nw);
   std::lock_guard<std::mutex> lk(g_mu);
-  if ((rc = reserve_scratch(dev, crcs ? size_t(B.nchunks) * 4 : 0, tab_bytes))) return rc;
-  if (iters && !g_s.ev[0] &&
-      (hipEventCreate(&g_s.ev[0]) != hipSuccess || hipEventCreate(&g_s.ev[1]) != hipSuccess))
-    return fail(HDFS_CRC32C_EHIP, "events: %s", hipGetErrorString(hipGetLastError()));
+  if ((rc = g_s.reserve(dev, crcs ? size_t(B.nchunks) * 4 : 0, tab_bytes)) || (iters && (rc = g_s.timing_events())))
+    return rc;
   // the tables, in pinned memory: the writes that have packets (the others are
   // dropped here, so the kernel's search never meets an empty entry) and the
   // prefix of their packet counts; the CRCs: every write's chunk grid as
-  // segments of one compute plan, the short first chunk and the 512-B grid
-  // behind it, write k's CRCs behind those of the writes ahead of it
-  Write *tab = static_cast<Write *>(g_s.pin);
+  // segments of one compute plan, write k's CRCs behind those of the writes
+  // ahead of it
+  Write *tab = g_s.pin.as<Write>();
   uint32_t *pk0 = reinterpret_cast<uint32_t *>(tab + nw);
   std::vector<hdfs_crc32c_segment> segs;
   if (crcs) segs.reserve(2 * size_t(nw));
-  const uint32_t sf = HDFS_CRC32C_SEG_BE | (ctype == HDFS_CRC32C_CSUM_CRC32 ? HDFS_CRC32C_SEG_CRC32 : 0u);
+  hdfs_crc32c_segment two[2];
   uint64_t c0 = 0;
   uint32_t e = 0;
   for (size_t k = 0; k < n; k++) {
@@ -312,14 +229,11 @@ int compose(hdfs_wire_batch_write *w, size_t n, int proto, int ctype, hdfs_crc32
     t = L.w;
     t.slices = kBatchSlices;
     t.data = static_cast<const uint8_t *>(w[k].data);
-    t.crc = g_s.crc + c0;
+    t.crc = g_s.crc.as<uint32_t>() + c0;
     t.wire = static_cast<uint8_t *>(w[k].wire);
     pk0[e++] = uint32_t(w[k].first_pkt);
     if (crcs && t.len) {
-      if (t.n0) segs.push_back(hdfs_crc32c_segment{t.data, t.n0, kChunk, sf, 0u, 0u, g_s.crc + c0, nullptr});
-      if (t.len > t.n0)
-        segs.push_back(hdfs_crc32c_segment{t.data + t.n0, t.len - t.n0, kChunk, sf, 0u, 0u,
-                                           g_s.crc + c0 + (t.n0 ? 1 : 0), nullptr});
+      segs.insert(segs.end(), two, two + grid_segments(t, g_s.crc.as<uint32_t>() + c0, ctype, two));
       c0 += L.nchunks;
     }
   }
@@ -329,25 +243,11 @@ int compose(hdfs_wire_batch_write *w, size_t n, int proto, int ctype, hdfs_crc32
   if (!segs.empty() && (rc = hdfs_crc32c_plan_create(&cplan, HDFS_CRC32C_MODE_COMPUTE, segs.data(), segs.size())))
     return engine_fail(rc, "compute plan");
   hipStream_t st = stream ? static_cast<hipStream_t>(stream) : g_s.st;
-  hipError_t he = hipMemcpyAsync(g_s.tab, g_s.pin, tab_bytes, hipMemcpyHostToDevice, st);
-  if (he == hipSuccess && cplan && (rc = hdfs_crc32c_plan_execute(cplan, st))) rc = engine_fail(rc, "compute plan");
-  if (!rc && he == hipSuccess) he = launch_frame_batch(g_s.tab, nw, total, st);
-  if (!rc && he == hipSuccess && iters) {
-    he = hipEventRecord(g_s.ev[0], st);
-    for (int i = 0; i < iters && he == hipSuccess; i++) he = launch_frame_batch(g_s.tab, nw, total, st);
-    if (he == hipSuccess) he = hipEventRecord(g_s.ev[1], st);
-  }
-  // always: the CRC array and the tables must be out of use before the lock goes
-  const hipError_t se = hipStreamSynchronize(st);
-  if (he == hipSuccess) he = se;
-  if (cplan) hdfs_crc32c_plan_destroy(cplan);
+  const hipError_t up = hipMemcpyAsync(g_s.tab.p, g_s.pin.p, tab_bytes, hipMemcpyHostToDevice, st);
+  // the CRC array and the tables are out of use when this returns, so before the lock goes
+  rc = timed_frame_run(st, up, cplan, g_s.ev, iters, ms_per_iter, "wire batch",
+                       [&] { return launch_frame_batch(g_s.tab.p, nw, total, st); });
   if (rc) return rc;
-  if (he == hipSuccess && iters) {
-    float ms = 0;
-    he = hipEventElapsedTime(&ms, g_s.ev[0], g_s.ev[1]);
-    if (ms_per_iter) *ms_per_iter = double(ms) / iters;
-  }
-  if (he != hipSuccess) return fail(HDFS_CRC32C_EHIP, "wire batch: %s", hipGetErrorString(he));
   if (fits) fill_batch_records(w, B, pkts);
   return HDFS_CRC32C_OK;
 }
@@ -361,7 +261,7 @@ extern "C" {
 
 int hdfs_wire_batch_abi_version(void) { return HDFS_WIRE_BATCH_ABI_VERSION; }
 
-const char *hdfs_wire_batch_last_error(void) { return g_err; }
+const char *hdfs_wire_batch_last_error(void) { return last_error(); }
 
 int hdfs_wire_batch_layout(hdfs_wire_batch_write *w, size_t nwrites, int proto, int ctype,
                            hdfs_wire_batch_totals *out) {

@@ -1,25 +1,23 @@
 // Host side shared by libhadoofus_wire.so (wire.cpp) and
-// libhadoofus_wire_batch.so (wire_batch.cpp): the layout of one write's
-// stream, its packet records and the check of where a buffer lives.  One
-// definition, included by both; each library keeps its own last-error text by
-// defining hdfs_wire::fail itself.
+// libhadoofus_wire_batch.so (wire_batch.cpp) only: the layout of one write's
+// stream, its packet records, the compute-plan segments of its chunk grid and
+// the timed frame run.  One definition, included by both.  What every
+// companion library shares (last error, DeviceGuard, device_range, ...) is
+// companion_support.h's.
 #ifndef HADOOFUS_WIRE_LAYOUT_H
 #define HADOOFUS_WIRE_LAYOUT_H
-
-#include <hip/hip_runtime.h>
 
 #include <cstring>
 #include <vector>
 
+#include "companion_support.h"
 #include "crc32c_outpkt.h"
 #include "hadoofus_crc32c.h"
 #include "wire_internal.h"
 
 namespace hdfs_wire {
 
-// Stores the calling thread's last-error text of the including library and
-// returns code.  Defined once by each library (wire.cpp, wire_batch.cpp).
-int fail(int code, const char *fmt, ...) __attribute__((format(printf, 2, 3)));
+using namespace hdfs_companion;
 
 static_assert(kChunk == hdfs_crc32c::outpkt::kWriteChunk && int64_t(kPacket) == hdfs_crc32c::outpkt::kPacketSize,
               "one packet geometry");
@@ -29,17 +27,6 @@ static_assert(kChunk == hdfs_crc32c::outpkt::kWriteChunk && int64_t(kPacket) == 
 // 1 GiB.
 constexpr uint32_t kSlices = 4;
 
-struct DeviceGuard {
-  int prev = -1;
-  bool changed = false;
-  explicit DeviceGuard(int dev) {
-    if (hipGetDevice(&prev) == hipSuccess && prev != dev) changed = hipSetDevice(dev) == hipSuccess;
-  }
-  ~DeviceGuard() {
-    if (changed) (void)hipSetDevice(prev);
-  }
-};
-
 // ---- layout -------------------------------------------------------------------
 struct Layout {
   Write w;  // pointers not set
@@ -48,10 +35,7 @@ struct Layout {
 };
 
 inline bool args_ok(int proto, int ctype, int64_t offset_in_block, uint64_t len) {
-  if (proto != HDFS_CRC32C_PROTO_V1 && proto != HDFS_CRC32C_PROTO_V2) return fail(HDFS_CRC32C_EINVAL, "proto must be 1 or 2"), false;
-  if (ctype != HDFS_CRC32C_CSUM_NULL && ctype != HDFS_CRC32C_CSUM_CRC32 && ctype != HDFS_CRC32C_CSUM_CRC32C)
-    return fail(HDFS_CRC32C_EINVAL, "bad checksum type %d", ctype), false;
-  if (offset_in_block < 0) return fail(HDFS_CRC32C_EINVAL, "negative block offset"), false;
+  if (!packet_args_ok(proto, ctype, offset_in_block)) return false;
   if (len > (uint64_t(1) << 40)) return fail(HDFS_CRC32C_EINVAL, "more than 1 TiB in one write"), false;
   return true;
 }
@@ -109,33 +93,42 @@ inline void fill_records(const Layout &L, hdfs_crc32c_out_packet *pkts) {
   }
 }
 
-// ---- where the buffers live -------------------------------------------------------
-// [p, p + n) inside one allocation of device `dev`.  alloc_lo / alloc_hi (may
-// be NULL): that allocation's address range, for a caller that checks many
-// ranges of one allocation.
-inline int device_range(const void *p, uint64_t n, int dev, const char *what, uintptr_t *alloc_lo = nullptr,
-                        uintptr_t *alloc_hi = nullptr) {
-  hipPointerAttribute_t a;
-  if (hipPointerGetAttributes(&a, p) != hipSuccess) {
-    (void)hipGetLastError();  // memory the runtime does not know: host
-    return fail(HDFS_CRC32C_EINVAL, "%s: %p is not device memory", what, p);
+// ---- the CRCs of a write ---------------------------------------------------------
+// compose_packets' chunk grid of write t as segments of a compute plan: the
+// short first chunk, then the 512-B grid behind it; chunk i's CRC goes to
+// crc[i].  out has room for two.  -> segments written (none without checksums
+// or data).
+inline size_t grid_segments(const Write &t, uint32_t *crc, int ctype, hdfs_crc32c_segment *out) {
+  if (ctype == HDFS_CRC32C_CSUM_NULL || !t.len) return 0;
+  const uint32_t sf = HDFS_CRC32C_SEG_BE | (ctype == HDFS_CRC32C_CSUM_CRC32 ? HDFS_CRC32C_SEG_CRC32 : 0u);
+  size_t ns = 0;
+  if (t.n0) out[ns++] = hdfs_crc32c_segment{t.data, t.n0, kChunk, sf, 0u, 0u, crc, nullptr};
+  if (t.len > t.n0)
+    out[ns++] = hdfs_crc32c_segment{t.data + t.n0, t.len - t.n0, kChunk, sf, 0u, 0u, crc + (t.n0 ? 1 : 0), nullptr};
+  return ns;
+}
+
+// ---- the frame run ------------------------------------------------------------------
+// On stream st, after whatever the caller enqueued with status e: the compute
+// plan (may be NULL), then launch() once.  iters > 0: then launch() iters more
+// times between the two events, and *ms_per_iter is one launch's time.  Always
+// synchronises and destroys the plan (sync_and_report).
+template <class Launch>
+int timed_frame_run(hipStream_t st, hipError_t e, hdfs_crc32c_plan *cplan, hipEvent_t *ev, int iters,
+                    double *ms_per_iter, const char *what, Launch launch) {
+  int rc = HDFS_CRC32C_OK;
+  if (e == hipSuccess && cplan && (rc = hdfs_crc32c_plan_execute(cplan, st))) rc = engine_fail(rc, "compute plan");
+  if (!rc && e == hipSuccess) e = launch();
+  if (!rc && e == hipSuccess && iters) {
+    e = hipEventRecord(ev[0], st);
+    for (int i = 0; i < iters && e == hipSuccess; i++) e = launch();
+    if (e == hipSuccess) e = hipEventRecord(ev[1], st);
   }
-  if (a.type != hipMemoryTypeDevice) return fail(HDFS_CRC32C_EINVAL, "%s: %p is not device memory", what, p);
-  if (a.device != dev)
-    return fail(HDFS_CRC32C_EINVAL, "%s: memory of device %d, the engine runs on device %d", what, a.device, dev);
-  void *ab = nullptr;
-  size_t as = 0;
-  if (hipMemGetAddressRange(&ab, &as, const_cast<void *>(p)) != hipSuccess) {
-    (void)hipGetLastError();
-    return fail(HDFS_CRC32C_EINVAL, "%s: no device allocation at %p", what, p);
-  }
-  const uintptr_t lo = reinterpret_cast<uintptr_t>(ab), b = reinterpret_cast<uintptr_t>(p);
-  if (b < lo || b - lo > as || n > as - (b - lo))
-    return fail(HDFS_CRC32C_EINVAL, "%s: %llu bytes at %p run past the end of their device allocation", what,
-                (unsigned long long)n, p);
-  if (alloc_lo) *alloc_lo = lo;
-  if (alloc_hi) *alloc_hi = lo + as;
-  return HDFS_CRC32C_OK;
+  if ((rc = sync_and_report(st, e, rc, cplan, what)) || !iters) return rc;
+  float ms = 0;
+  e = hipEventElapsedTime(&ms, ev[0], ev[1]);
+  if (ms_per_iter) *ms_per_iter = double(ms) / iters;
+  return e == hipSuccess ? HDFS_CRC32C_OK : fail(HDFS_CRC32C_EHIP, "%s: %s", what, hipGetErrorString(e));
 }
 
 }  // namespace hdfs_wire

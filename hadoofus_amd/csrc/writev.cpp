@@ -6,13 +6,12 @@
 // as one compute plan of that library, and both share one HIP runtime.
 #include <hip/hip_runtime.h>
 
-#include <cstdarg>
-#include <cstdio>
 #include <cstring>
 #include <memory>
 #include <mutex>
 #include <vector>
 
+#include "companion_support.h"
 #include "crc32c_outpkt.h"
 #include "crc32c_tables.h"
 #include "hadoofus_writev.h"
@@ -21,6 +20,7 @@
 namespace hdfs_writev {
 namespace {
 
+using namespace hdfs_companion;
 using namespace hdfs_crc32c::outpkt;
 
 // A run of whole chunks inside one fragment shorter than this is not worth a
@@ -29,30 +29,6 @@ using namespace hdfs_crc32c::outpkt;
 // tile there, filled to less than its width, for the price of a table entry.
 constexpr uint32_t kMinSegChunks = 8;
 constexpr uint64_t kHostWindow = uint64_t(64) << 20;  // host fragments: bytes packed per call of the main library
-
-thread_local char g_err[512] = "";
-
-int fail(int code, const char *fmt, ...) {
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(g_err, sizeof(g_err), fmt, ap);
-  va_end(ap);
-  return code;
-}
-
-// A failure of the main library is this call's failure, with its text.
-int engine_fail(int rc, const char *what) { return fail(rc, "%s: %s", what, hdfs_crc32c_last_error()); }
-
-struct DeviceGuard {
-  int prev = -1;
-  bool changed = false;
-  explicit DeviceGuard(int dev) {
-    if (hipGetDevice(&prev) == hipSuccess && prev != dev) changed = hipSetDevice(dev) == hipSuccess;
-  }
-  ~DeviceGuard() {
-    if (changed) (void)hipSetDevice(prev);
-  }
-};
 
 // ---- layout -----------------------------------------------------------------
 // A run of whole chunks [chunk0, chunk0 + ...) inside fragment `frag`.
@@ -148,74 +124,46 @@ int build_layout(const uint64_t *lens, const void *const *bases, int n, int64_t 
 // calls.  Calls hold g_mu from the uploads to the final synchronise, so one
 // call's tables are never overwritten under its kernels.
 std::mutex g_mu;
-struct Scratch {
-  int dev = -1;
-  hipStream_t st = nullptr;
+// The pinned landing area is the engine's pin registry's, not the runtime's.
+int landing_alloc(void **p, size_t n) {
+  const int rc = hdfs_crc32c_host_alloc(p, n);
+  return rc ? engine_fail(rc, "pinned CRC landing area") : rc;
+}
+void landing_free(void *p) { (void)hdfs_crc32c_host_free(p); }
+
+struct Scratch : DeviceScratch {
   uint32_t *slice = nullptr;  // u32[2][kSliceWords]: CRC32C, CRC32
-  uint8_t *crc = nullptr, *tab = nullptr;
-  size_t crc_cap = 0, tab_cap = 0;
-  void *h_crc = nullptr;  // pinned (hdfs_crc32c_host_alloc)
-  size_t h_cap = 0;
+  DeviceBuffer crc, tab;
+  PinnedBuffer<landing_alloc, landing_free> h_crc;
+
+  int reserve(int to, size_t crc_bytes, size_t tab_bytes) {
+    auto release_own = [this] {
+      if (slice) (void)hipFree(slice);
+      slice = nullptr;
+      crc.release();
+      tab.release();
+      h_crc.release();
+    };
+    int rc = bind(to, "stream and tables", release_own);
+    if (rc) return rc;
+    if (!slice) {  // bound anew: the slicing tables
+      hipError_t e = hipMalloc(&slice, 2 * kSliceWords * sizeof(uint32_t));
+      if (e != hipSuccess) slice = nullptr;
+      if (e == hipSuccess) {
+        std::vector<uint32_t> t(2 * kSliceWords);
+        hdfs_crc32c::make_slicing4(reinterpret_cast<uint32_t(*)[256]>(t.data()), hdfs_crc32c::kPoly);
+        hdfs_crc32c::make_slicing4(reinterpret_cast<uint32_t(*)[256]>(t.data() + kSliceWords), hdfs_crc32c::kPolyZlib);
+        e = hipMemcpy(slice, t.data(), t.size() * sizeof(uint32_t), hipMemcpyHostToDevice);
+      }
+      if (e != hipSuccess) {
+        unbind(release_own);
+        return fail(HDFS_CRC32C_EHIP, "stream and tables: %s", hipGetErrorString(e));
+      }
+    }
+    if ((rc = crc.reserve(crc_bytes, kScratchFloor)) || (rc = tab.reserve(tab_bytes, kScratchFloor))) return rc;
+    return h_crc.reserve(crc_bytes, kScratchFloor);
+  }
 } g_s;
-
-void release_scratch() {
-  if (g_s.st) (void)hipStreamSynchronize(g_s.st);
-  if (g_s.slice) (void)hipFree(g_s.slice);
-  if (g_s.crc) (void)hipFree(g_s.crc);
-  if (g_s.tab) (void)hipFree(g_s.tab);
-  if (g_s.h_crc) (void)hdfs_crc32c_host_free(g_s.h_crc);
-  if (g_s.st) (void)hipStreamDestroy(g_s.st);
-  g_s = Scratch{};
-}
-
-int grow(uint8_t *&p, size_t &cap, size_t need) {
-  if (need <= cap) return HDFS_CRC32C_OK;
-  if (p) (void)hipFree(p);
-  p = nullptr;
-  cap = 0;
-  const size_t want = need < (64u << 10) ? (64u << 10) : need;
-  if (hipMalloc(&p, want) != hipSuccess) {
-    (void)hipGetLastError();
-    p = nullptr;
-    return fail(HDFS_CRC32C_ENOMEM, "device allocation of %zu bytes failed", want);
-  }
-  cap = want;
-  return HDFS_CRC32C_OK;
-}
-
-int reserve_scratch(int dev, size_t crc_bytes, size_t tab_bytes) {
-  if (g_s.dev != dev) {
-    if (g_s.dev >= 0) {
-      DeviceGuard g(g_s.dev);
-      release_scratch();
-    }
-    // a blocking stream: ordered after work queued earlier on the NULL stream
-    hipError_t e = hipStreamCreate(&g_s.st);
-    if (e == hipSuccess) e = hipMalloc(&g_s.slice, 2 * kSliceWords * sizeof(uint32_t));
-    if (e == hipSuccess) {
-      std::vector<uint32_t> t(2 * kSliceWords);
-      hdfs_crc32c::make_slicing4(reinterpret_cast<uint32_t(*)[256]>(t.data()), hdfs_crc32c::kPoly);
-      hdfs_crc32c::make_slicing4(reinterpret_cast<uint32_t(*)[256]>(t.data() + kSliceWords), hdfs_crc32c::kPolyZlib);
-      e = hipMemcpy(g_s.slice, t.data(), t.size() * sizeof(uint32_t), hipMemcpyHostToDevice);
-    }
-    if (e != hipSuccess) {
-      release_scratch();
-      return fail(HDFS_CRC32C_EHIP, "stream and tables: %s", hipGetErrorString(e));
-    }
-    g_s.dev = dev;
-  }
-  int rc;
-  if ((rc = grow(g_s.crc, g_s.crc_cap, crc_bytes)) || (rc = grow(g_s.tab, g_s.tab_cap, tab_bytes))) return rc;
-  if (crc_bytes > g_s.h_cap) {
-    if (g_s.h_crc) (void)hdfs_crc32c_host_free(g_s.h_crc);
-    g_s.h_crc = nullptr;
-    g_s.h_cap = 0;
-    const size_t want = crc_bytes < (64u << 10) ? (64u << 10) : crc_bytes;
-    if ((rc = hdfs_crc32c_host_alloc(&g_s.h_crc, want))) return engine_fail(rc, "pinned CRC landing area");
-    g_s.h_cap = want;
-  }
-  return HDFS_CRC32C_OK;
-}
 
 // ---- where the fragments live ---------------------------------------------------
 // All device memory of device `dev` (each inside one allocation) or all host
@@ -227,24 +175,15 @@ int classify(const hdfs_crc32c_iovec *iov, int n, int dev, bool *on_device) {
   for (int i = 0; i < n; i++) {
     if (!iov[i].len) continue;
     const uintptr_t b = reinterpret_cast<uintptr_t>(iov[i].base);
-    bool d = false;
-    if (b >= lo && b < hi) {
-      d = true;
-    } else {
-      hipPointerAttribute_t a;
-      if (hipPointerGetAttributes(&a, iov[i].base) != hipSuccess) {
-        (void)hipGetLastError();  // memory the runtime does not know: host
-      } else if (a.type == hipMemoryTypeDevice) {
-        if (a.device != dev)
-          return fail(HDFS_CRC32C_EINVAL, "fragment %d: memory of device %d, the engine runs on device %d", i, a.device, dev);
-        void *ab = nullptr;
-        size_t as = 0;
-        if (hipMemGetAddressRange(&ab, &as, iov[i].base) != hipSuccess) {
-          (void)hipGetLastError();
-          return fail(HDFS_CRC32C_EINVAL, "fragment %d: no device allocation at %p", i, iov[i].base);
-        }
-        lo = reinterpret_cast<uintptr_t>(ab);
-        hi = lo + as;
+    bool d = b >= lo && b < hi;
+    if (!d) {
+      const Placement w = placement(iov[i].base, dev);
+      if (w.kind == Placement::kDevice) {  // memory the runtime does not know is host memory
+        if (w.device != dev)
+          return fail(HDFS_CRC32C_EINVAL, "fragment %d: memory of device %d, the engine runs on device %d", i, w.device, dev);
+        if (!w.hi) return fail(HDFS_CRC32C_EINVAL, "fragment %d: no device allocation at %p", i, iov[i].base);
+        lo = w.lo;
+        hi = w.hi;
         d = true;
       }
     }
@@ -271,11 +210,11 @@ int compose_device(const hdfs_crc32c_iovec *iov, const Layout &L, int dev, const
   const size_t ch_bytes = size_t(I.ngathered) * sizeof(GChunk), pc_bytes = size_t(I.npieces) * sizeof(Piece);
   DeviceGuard g(dev);
   std::lock_guard<std::mutex> lk(g_mu);
-  int rc = reserve_scratch(dev, crc_bytes, ch_bytes + pc_bytes);
+  int rc = g_s.reserve(dev, crc_bytes, ch_bytes + pc_bytes);
   if (rc) return rc;
-  uint32_t *d_crc = reinterpret_cast<uint32_t *>(g_s.crc);
-  GChunk *d_ch = reinterpret_cast<GChunk *>(g_s.tab);
-  Piece *d_pc = reinterpret_cast<Piece *>(g_s.tab + ch_bytes);
+  uint32_t *d_crc = g_s.crc.as<uint32_t>();
+  GChunk *d_ch = g_s.tab.as<GChunk>();
+  Piece *d_pc = reinterpret_cast<Piece *>(g_s.tab.as<uint8_t>() + ch_bytes);
   const bool zlib = ctype == HDFS_CRC32C_CSUM_CRC32;
   // in place: every run is one segment of one compute plan, its CRCs at the
   // run's place in the write's CRC array
@@ -299,14 +238,10 @@ int compose_device(const hdfs_crc32c_iovec *iov, const Layout &L, int dev, const
   if (e == hipSuccess && !rc)
     e = launch_gather_chunks(d_ch, uint32_t(I.ngathered), d_pc, uint32_t(I.npieces), g_s.slice + (zlib ? kSliceWords : 0),
                              d_crc, uint32_t(I.nchunks), st);
-  if (e == hipSuccess && !rc) e = hipMemcpyAsync(g_s.h_crc, d_crc, crc_bytes, hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess && !rc) e = hipMemcpyAsync(g_s.h_crc.p, d_crc, crc_bytes, hipMemcpyDeviceToHost, st);
   // always: the tables and the CRC array must be out of use before the lock goes
-  const hipError_t se = hipStreamSynchronize(st);
-  if (e == hipSuccess) e = se;
-  if (cplan) hdfs_crc32c_plan_destroy(cplan);
-  if (rc) return rc;
-  if (e != hipSuccess) return fail(HDFS_CRC32C_EHIP, "gather write: %s", hipGetErrorString(e));
-  const uint32_t *crcs = static_cast<const uint32_t *>(g_s.h_crc);
+  if ((rc = sync_and_report(st, e, rc, cplan, "gather write"))) return rc;
+  const uint32_t *crcs = g_s.h_crc.as<const uint32_t>();
   write_out_packets(plan, proto, true, L.n0, crcs, crcs + (L.n0 ? 1 : 0), hdr_out, pkts);
   return HDFS_CRC32C_OK;
 }
@@ -355,13 +290,7 @@ int compose_host(const hdfs_crc32c_iovec *iov, uint64_t total, int64_t off, int6
   return HDFS_CRC32C_OK;
 }
 
-bool args_ok(int proto, int ctype, int64_t offset_in_block) {
-  if (proto != HDFS_CRC32C_PROTO_V1 && proto != HDFS_CRC32C_PROTO_V2) return fail(HDFS_CRC32C_EINVAL, "proto must be 1 or 2"), false;
-  if (ctype != HDFS_CRC32C_CSUM_NULL && ctype != HDFS_CRC32C_CSUM_CRC32 && ctype != HDFS_CRC32C_CSUM_CRC32C)
-    return fail(HDFS_CRC32C_EINVAL, "bad checksum type %d", ctype), false;
-  if (offset_in_block < 0) return fail(HDFS_CRC32C_EINVAL, "negative block offset"), false;
-  return true;
-}
+bool args_ok(int proto, int ctype, int64_t offset_in_block) { return packet_args_ok(proto, ctype, offset_in_block); }
 
 }  // namespace
 }  // namespace hdfs_writev
@@ -372,7 +301,7 @@ extern "C" {
 
 int hdfs_writev_abi_version(void) { return HDFS_WRITEV_ABI_VERSION; }
 
-const char *hdfs_writev_last_error(void) { return g_err; }
+const char *hdfs_writev_last_error(void) { return last_error(); }
 
 int hdfs_writev_layout(const uint64_t *lens, int iovcnt, int64_t offset_in_block, hdfs_writev_layout_info *out) {
   if (!out) return fail(HDFS_CRC32C_EINVAL, "null out");
@@ -421,9 +350,7 @@ int hdfs_writev_compose_packets(const hdfs_crc32c_iovec *iov, int iovcnt, int64_
     return rc ? engine_fail(rc, "compose_packets") : rc;
   }
   int dev = -1;
-  rc = hdfs_crc32c_init(-1);
-  if (rc == HDFS_CRC32C_OK) rc = hdfs_crc32c_bound_device(&dev, nullptr, 0);
-  if (rc) return engine_fail(rc, "engine");
+  if ((rc = engine_device(&dev))) return rc;
   bool on_device = false;
   {
     DeviceGuard g(dev);

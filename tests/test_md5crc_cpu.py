@@ -15,6 +15,8 @@ import sys
 import numpy as np
 import pytest
 
+from abi_symbols import declared as _declared, exported as _exported
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 EINVAL = -1
 
@@ -30,25 +32,6 @@ def libs():
 def h(libs):
     import hadoofus_amd
     return hadoofus_amd
-
-
-def _declared(header):
-    src = open(os.path.join(ROOT, "include", header)).read()
-    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
-    src = "\n".join(l for l in src.splitlines() if not l.lstrip().startswith("#"))
-    src = re.sub(r"typedef\s+struct\s+\w*\s*\{.*?\}\s*\w+\s*;", " ", src, flags=re.S)
-    return set(re.findall(r"\b([A-Za-z_][A-Za-z0-9_]*)\s*\([^;{]*\)\s*;", src)) - {"sizeof"}
-
-
-def _exported(path):
-    """{name: version node} of the defined dynamic function symbols."""
-    out = subprocess.check_output(["objdump", "-T", path], text=True)
-    seen = {}
-    for line in out.splitlines():
-        parts = line.split()
-        if len(parts) >= 6 and parts[1] == "g" and "DF" in parts and ".text" in parts:
-            seen[parts[-1]] = parts[-2]
-    return seen
 
 
 # ---- host MD5 ---------------------------------------------------------------

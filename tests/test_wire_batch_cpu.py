@@ -12,6 +12,8 @@ import sys
 import numpy as np
 import pytest
 
+from abi_symbols import c_functions as _c_functions, declared as _declared, exported as _exported
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 EINVAL = -1
 DECLARED = {"hdfs_wire_batch_abi_version", "hdfs_wire_batch_last_error", "hdfs_wire_batch_compose",
@@ -188,30 +190,6 @@ def test_layout_and_timing_argument_errors(wb):
 
 
 # ---- build and ABI ------------------------------------------------------------------
-def _declared(header):
-    src = open(os.path.join(ROOT, "include", header)).read()
-    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
-    src = "\n".join(l for l in src.splitlines() if not l.lstrip().startswith("#"))
-    src = re.sub(r"typedef\s+struct\s+\w*\s*\{.*?\}\s*\w+\s*;", " ", src, flags=re.S)
-    return set(re.findall(r"\b([A-Za-z_][A-Za-z0-9_]*)\s*\([^;{]*\)\s*;", src)) - {"sizeof"}
-
-
-def _exported(path):
-    """{name: version node} of the defined dynamic function symbols."""
-    out = subprocess.check_output(["objdump", "-T", path], text=True)
-    seen = {}
-    for line in out.splitlines():
-        parts = line.split()
-        if len(parts) >= 6 and parts[1] == "g" and "DF" in parts and ".text" in parts:
-            seen[parts[-1]] = parts[-2]
-    return seen
-
-
-def _c_functions(path):
-    return {n: v for n, v in _exported(path).items()
-            if n not in ("_init", "_fini") and not (n.startswith("_ZN") and "_kernel" in n)}
-
-
 def test_build_produces_the_library(libs):
     lib, blib = libs
     assert os.path.exists(blib) and os.path.basename(blib) == "libhadoofus_wire_batch.so"
@@ -223,6 +201,8 @@ def test_build_lists_sources_and_headers():
     assert build.WIRE_BATCH_SOURCES == ["wire_batch_kernels.hip", "wire_batch.cpp"]
     assert {"wire_batch_internal.h", "wire_frame.h", "wire_layout.h", "wire_internal.h", "crc32c_outpkt.h",
             "wire_batch_exports.map"} <= set(build.WIRE_BATCH_HEADERS)
+    for headers in (build.MD5CRC_HEADERS, build.WRITEV_HEADERS, build.WIRE_HEADERS, build.WIRE_BATCH_HEADERS):
+        assert "companion_support.h" in headers
     assert "hadoofus_wire_batch.h" in build.WIRE_BATCH_PUBLIC and build.ARCH == "gfx950"
     assert build.WIRE_SOURCES == ["wire_kernels.hip", "wire.cpp"]
     assert {"wire_frame.h", "wire_layout.h"} <= set(build.WIRE_HEADERS)
@@ -235,22 +215,39 @@ def test_build_lists_sources_and_headers():
 
 
 def test_one_definition_of_the_framing_and_layout_code():
-    """The framing body lives in wire_frame.h and the layout code in
-    wire_layout.h; the four sources of the two libraries include them and hold
-    no copy, nor one of the header-writing code of crc32c_outpkt.h."""
+    """The framing body lives in wire_frame.h, the layout code, the plan
+    segments of a write and the timed frame run in wire_layout.h, and what all
+    four companions share in companion_support.h; the sources of the libraries
+    include them and hold no copy, nor one of the header-writing code of
+    crc32c_outpkt.h."""
     from hadoofus_amd import build
     read = lambda f: open(os.path.join(build.CSRC, f)).read()  # noqa: E731
     device = ["copy_region(", "copy_header(", "cut16(", "shift_window(", "void issue(", "frame_packet("]
-    host = ["int build_layout(", "void fill_records(", "int device_range(", "bool args_ok("]
-    frame, lay = read("wire_frame.h"), read("wire_layout.h")
+    host = ["int build_layout(", "void fill_records(", "bool args_ok(", "size_t grid_segments("]
+    support = ["int device_range(", "int fail(", "int engine_fail(", "int prefix_fail(", "int engine_device(",
+               "bool packet_args_ok(", "int sync_and_report(", "Placement placement("]
+    frame, lay, sup = read("wire_frame.h"), read("wire_layout.h"), read("companion_support.h")
+    cpps = ("md5crc.cpp", "writev.cpp", "wire.cpp", "wire_batch.cpp")
     for name in device:
         assert len(re.findall(r"WIRE_DEV [\w:<> ]*\b" + re.escape(name), frame)) == 1, name
     for name in host:
-        assert frame.count(name) == 0 and lay.count("inline " + name) == 1, name
+        assert frame.count(name) == 0 and sup.count(name) == 0 and lay.count("inline " + name) == 1, name
+    assert lay.count("\nint timed_frame_run(") == 1 and "timed_frame_run" not in sup + frame
+    # companion_support.h: exactly one definition, none in wire_layout.h or in any of the four sources
+    for name in support:
+        assert sup.count("inline " + name) == 1 and sup.count(name) == 1, name
+        for f in ("wire_layout.h", "wire_frame.h") + cpps:
+            assert name not in read(f), (f, name)
+    for name in ("struct DeviceGuard", "struct DeviceScratch", "struct GrowOnly", "struct Allocations",
+                 "thread_local char g_err"):
+        assert sup.count(name) == 1, name
+        for f in ("wire_layout.h", "wire_frame.h") + cpps:
+            assert name not in read(f), (f, name)
+    assert '#include "companion_support.h"' in lay
     for f in ("wire_kernels.hip", "wire_batch_kernels.hip"):
         src = read(f)
         assert '#include "wire_frame.h"' in src and "frame::frame_packet<" in src, f
-        for name in device[:-1] + host:
+        for name in device[:-1] + host + support:
             assert name not in src, (f, name)
         assert "v_alignbyte" not in src and "alignbyte(" not in src and "global_store" not in src, f
     for f in ("wire.cpp", "wire_batch.cpp"):
@@ -258,7 +255,18 @@ def test_one_definition_of_the_framing_and_layout_code():
         assert '#include "wire_layout.h"' in src, f
         for name in host:
             assert not re.search(r"^\w[\w ]*\b" + re.escape(name), src, flags=re.M), (f, name)
-        assert "hipPointerGetAttributes" not in src and "plan_out_packets(" not in src, f
+        assert "plan_out_packets(" not in src and "timed_frame_run(" in src and "grid_segments(" in src, f
+        for gone in ("hipStreamSynchronize", "hipEventRecord", "hdfs_crc32c_plan_execute", "HDFS_CRC32C_SEG_BE"):
+            assert gone not in src, (f, gone)  # the run and the segments are wire_layout.h's alone
+    # the pointer queries of all four libraries are companion_support.h's; no kernel file includes it
+    companion = set(build.MD5CRC_SOURCES + build.MD5CRC_HEADERS + build.WRITEV_SOURCES + build.WRITEV_HEADERS +
+                    build.WIRE_SOURCES + build.WIRE_HEADERS + build.WIRE_BATCH_SOURCES + build.WIRE_BATCH_HEADERS)
+    for f in sorted(companion - {"companion_support.h"}):
+        src = read(f)
+        assert "hipPointerGetAttributes" not in src and "hipMemGetAddressRange" not in src, f
+        assert f.endswith(".cpp") or f == "wire_layout.h" or "companion_support.h" not in src, f
+    for f in cpps:
+        assert "companion_support.h" in read(f) or '#include "wire_layout.h"' in read(f), f
     for f in build.WIRE_SOURCES + build.WIRE_BATCH_SOURCES + ["wire_frame.h", "wire_layout.h", "wire_batch_internal.h"]:
         src = read(f)
         assert "put_header_proto(uint8_t" not in src and "put_out_header(uint8_t" not in src, f
@@ -369,16 +377,36 @@ def test_abi_version_call_and_binding_check(wb):
 
 
 def test_last_error_texts_are_separate(wb):
-    """Each library keeps its own text, though both compile wire_layout.h."""
-    from hadoofus_amd import wire
-    wl, bl = wire.load(), wb.load()
-    info = wire.LayoutInfo()
-    assert wl.hdfs_wire_layout(10, -1, 2, 2, 0, ctypes.byref(info)) == EINVAL
-    single = wl.hdfs_wire_last_error()
-    tot = wb.Totals()
-    assert bl.hdfs_wire_batch_layout(wb.entries([wb.write(nbytes=1)], True), 1, 7, 2, ctypes.byref(tot)) == EINVAL
-    assert b"proto" in bl.hdfs_wire_batch_last_error() and wl.hdfs_wire_last_error() == single
-    assert b"proto" not in single
+    """Each of the four libraries keeps its own text, though all compile
+    companion_support.h and two of them wire_layout.h: an EINVAL provoked in
+    one, on a path that needs no device, leaves the other three texts alone."""
+    from hadoofus_amd import md5crc, wire, writev
+    wl, bl, vl, ml = wire.load(), wb.load(), writev.load(), md5crc.load()
+    info, tot, vinfo = wire.LayoutInfo(), wb.Totals(), writev.LayoutInfo()
+    one = wb.entries([wb.write(nbytes=1)], True)
+    provoke = {
+        "wire": (lambda: wl.hdfs_wire_layout(10, -1, 2, 2, 0, ctypes.byref(info)), b"negative block offset"),
+        "wire_batch": (lambda: bl.hdfs_wire_batch_layout(one, 1, 7, 2, ctypes.byref(tot)),
+                       b"entry 0: proto must be 1 or 2"),
+        "writev": (lambda: vl.hdfs_writev_layout(None, -1, 0, ctypes.byref(vinfo)), b"null or negative fragment list"),
+        "md5crc": (lambda: ml.hdfs_md5crc_md5_host(None, 5, None), b"null buffer / out"),
+    }
+    text = {"wire": wl.hdfs_wire_last_error, "wire_batch": bl.hdfs_wire_batch_last_error,
+            "writev": vl.hdfs_writev_last_error, "md5crc": ml.hdfs_md5crc_last_error}
+    for name, (call, want) in provoke.items():
+        before = {k: f() for k, f in text.items()}
+        assert call() == EINVAL and text[name]() == want, name
+        for k, f in text.items():
+            assert k == name or f() == before[k], (name, k)
+    assert len({f() for f in text.values()}) == 4
+    # the two that compile wire_layout.h, on the same shared code path
+    assert bl.hdfs_wire_batch_layout(wb.entries([wb.write(nbytes=1, offset_in_block=-1)], True), 1, 2, 2,
+                                     ctypes.byref(tot)) == EINVAL
+    assert bl.hdfs_wire_batch_last_error() == b"entry 0: negative block offset"
+    assert wl.hdfs_wire_last_error() == b"negative block offset"
+    assert wl.hdfs_wire_layout(10, 0, 7, 2, 0, ctypes.byref(info)) == EINVAL
+    assert wl.hdfs_wire_last_error() == b"proto must be 1 or 2"
+    assert bl.hdfs_wire_batch_last_error() == b"entry 0: negative block offset"
 
 
 def test_import_loads_nothing():

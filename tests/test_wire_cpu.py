@@ -11,6 +11,8 @@ import sys
 import numpy as np
 import pytest
 
+from abi_symbols import declared as _declared, exported as _exported
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 EINVAL = -1
 DECLARED = {"hdfs_wire_abi_version", "hdfs_wire_last_error", "hdfs_wire_compose_packets", "hdfs_wire_layout",
@@ -131,25 +133,6 @@ def test_layout_and_timing_argument_errors(wr):
 
 
 # ---- build and ABI ------------------------------------------------------------------
-def _declared(header):
-    src = open(os.path.join(ROOT, "include", header)).read()
-    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
-    src = "\n".join(l for l in src.splitlines() if not l.lstrip().startswith("#"))
-    src = re.sub(r"typedef\s+struct\s+\w*\s*\{.*?\}\s*\w+\s*;", " ", src, flags=re.S)
-    return set(re.findall(r"\b([A-Za-z_][A-Za-z0-9_]*)\s*\([^;{]*\)\s*;", src)) - {"sizeof"}
-
-
-def _exported(path):
-    """{name: version node} of the defined dynamic function symbols."""
-    out = subprocess.check_output(["objdump", "-T", path], text=True)
-    seen = {}
-    for line in out.splitlines():
-        parts = line.split()
-        if len(parts) >= 6 and parts[1] == "g" and "DF" in parts and ".text" in parts:
-            seen[parts[-1]] = parts[-2]
-    return seen
-
-
 def test_build_produces_the_library(libs):
     lib, wlib = libs
     assert os.path.exists(wlib) and os.path.basename(wlib) == "libhadoofus_wire.so"
@@ -160,6 +143,8 @@ def test_build_lists_sources_and_headers():
     from hadoofus_amd import build
     assert build.WIRE_SOURCES == ["wire_kernels.hip", "wire.cpp"]
     assert {"wire_internal.h", "crc32c_outpkt.h", "wire_exports.map"} <= set(build.WIRE_HEADERS)
+    for headers in (build.MD5CRC_HEADERS, build.WRITEV_HEADERS, build.WIRE_HEADERS, build.WIRE_BATCH_HEADERS):
+        assert "companion_support.h" in headers
     assert "hadoofus_wire.h" in build.WIRE_PUBLIC and build.ARCH == "gfx950"
     for f in build.WIRE_SOURCES + build.WIRE_HEADERS:
         assert os.path.exists(os.path.join(build.CSRC, f)), f

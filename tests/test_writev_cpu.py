@@ -13,6 +13,8 @@ import sys
 import numpy as np
 import pytest
 
+from abi_symbols import declared as _declared, exported as _exported
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 EINVAL = -1
 CS = 512
@@ -227,25 +229,6 @@ def test_argument_errors_are_einval_without_a_device(wv):
 
 
 # ---- build and ABI ------------------------------------------------------------------
-def _declared(header):
-    src = open(os.path.join(ROOT, "include", header)).read()
-    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
-    src = "\n".join(l for l in src.splitlines() if not l.lstrip().startswith("#"))
-    src = re.sub(r"typedef\s+struct\s+\w*\s*\{.*?\}\s*\w+\s*;", " ", src, flags=re.S)
-    return set(re.findall(r"\b([A-Za-z_][A-Za-z0-9_]*)\s*\([^;{]*\)\s*;", src)) - {"sizeof"}
-
-
-def _exported(path):
-    """{name: version node} of the defined dynamic function symbols."""
-    out = subprocess.check_output(["objdump", "-T", path], text=True)
-    seen = {}
-    for line in out.splitlines():
-        parts = line.split()
-        if len(parts) >= 6 and parts[1] == "g" and "DF" in parts and ".text" in parts:
-            seen[parts[-1]] = parts[-2]
-    return seen
-
-
 def test_build_produces_the_library(libs):
     lib, wlib = libs
     assert os.path.exists(wlib) and os.path.basename(wlib) == "libhadoofus_writev.so"
@@ -255,6 +238,9 @@ def test_build_produces_the_library(libs):
 def test_build_lists_the_shared_header_for_both_libraries():
     from hadoofus_amd import build
     assert "crc32c_outpkt.h" in build.HEADERS and "crc32c_outpkt.h" in build.WRITEV_HEADERS
+    for headers in (build.MD5CRC_HEADERS, build.WRITEV_HEADERS, build.WIRE_HEADERS, build.WIRE_BATCH_HEADERS):
+        assert "companion_support.h" in headers
+    assert "companion_support.h" not in build.HEADERS  # the main library has no part in it
     for f in build.WRITEV_SOURCES + build.WRITEV_HEADERS:
         assert os.path.exists(os.path.join(build.CSRC, f)), f
     # one definition of the header-writing code, not a copy
