@@ -13,7 +13,9 @@ list of device buffers) live in libhadoofus_writev.so, loaded the same way
 (include/hadoofus_wire.h: what verify_packets / read_packets consume) live in
 libhadoofus_wire.so, loaded the same way (wire.py); the streams of a batch of
 writes in one call (include/hadoofus_wire_batch.h) in
-libhadoofus_wire_batch.so (wire_batch.py).
+libhadoofus_wire_batch.so (wire_batch.py); a write held in a list of device
+buffers as one such stream (include/hadoofus_wirev.h) in libhadoofus_wirev.so
+(wirev.py).
 """
 from .abi import (  # noqa: F401
     LIB_PATH, bind_product, bind_diag, CSUM_NULL, CSUM_CRC32, CSUM_CRC32C, ERR_BAD_CHECKSUM, ERR_CRC_LEN,
@@ -31,5 +33,6 @@ from .md5crc import (  # noqa: F401  (binds nothing until first use)
 from .writev import compose_packets_iov, layout as writev_layout  # noqa: F401  (binds nothing until first use)
 from .wire import compose_wire, layout as wire_layout  # noqa: F401  (binds nothing until first use)
 from .wire_batch import compose_wire_batch, layout as wire_batch_layout  # noqa: F401  (binds nothing until first use)
+from .wirev import compose_wire as compose_wire_iov, layout as wirev_layout  # noqa: F401  (binds nothing until first use)
 
 __all__ = [n for n in dir() if not n.startswith("_")]

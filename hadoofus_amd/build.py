@@ -11,16 +11,19 @@ tools/ experiments and bench.py's ceiling measurement load it; the product
 library contains none of that code and reads no tuning knob from the
 environment.
 
-Four companion libraries link against the release library and are built
+Five companion libraries link against the release library and are built
 after it: libhadoofus_md5crc.so (include/hadoofus_md5crc.h),
 libhadoofus_writev.so (include/hadoofus_writev.h), libhadoofus_wire.so
-(include/hadoofus_wire.h) and libhadoofus_wire_batch.so
-(include/hadoofus_wire_batch.h), each with its own sources and export map.
-All four share the host support of companion_support.h (last error, the
+(include/hadoofus_wire.h), libhadoofus_wire_batch.so
+(include/hadoofus_wire_batch.h) and libhadoofus_wirev.so
+(include/hadoofus_wirev.h), each with its own sources and export map.
+All five share the host support of companion_support.h (last error, the
 engine's device, grow-only buffers, scratch bound to a device, pointer
-placement, the end of a call); the last two also share the framing and layout
-code of wire_frame.h and wire_layout.h.  These headers are compiled into
-every library that includes them, each keeping its own copy.
+placement, the end of a call); the wire libraries also share the framing and
+layout code of wire_frame.h and wire_layout.h, and the gather libraries
+(writev, wirev) the gather layout of writev_layout.h and the kernel of
+writev_kernels.hip.  These files are compiled into every library that uses
+them, each keeping its own copy; no companion links another.
 """
 import os
 import subprocess
@@ -44,8 +47,8 @@ MD5CRC_HEADERS = ["md5_core.h", "md5crc_internal.h", "companion_support.h", "md5
 MD5CRC_PUBLIC = ["hadoofus_md5crc.h", "hadoofus_crc32c.h"]
 WRITEV_LIB = os.path.join(LIBDIR, "libhadoofus_writev.so")
 WRITEV_SOURCES = ["writev_kernels.hip", "writev.cpp"]
-WRITEV_HEADERS = ["writev_internal.h", "crc32c_outpkt.h", "crc32c_tables.h", "companion_support.h",
-                  "writev_exports.map"]
+WRITEV_HEADERS = ["writev_internal.h", "writev_layout.h", "crc32c_outpkt.h", "crc32c_tables.h",
+                  "companion_support.h", "writev_exports.map"]
 WRITEV_PUBLIC = ["hadoofus_writev.h", "hadoofus_crc32c.h"]
 WIRE_LIB = os.path.join(LIBDIR, "libhadoofus_wire.so")
 WIRE_SOURCES = ["wire_kernels.hip", "wire.cpp"]
@@ -57,6 +60,11 @@ WIRE_BATCH_SOURCES = ["wire_batch_kernels.hip", "wire_batch.cpp"]
 WIRE_BATCH_HEADERS = ["wire_batch_internal.h", "wire_internal.h", "wire_frame.h", "wire_layout.h",
                       "companion_support.h", "crc32c_outpkt.h", "wire_batch_exports.map"]
 WIRE_BATCH_PUBLIC = ["hadoofus_wire_batch.h", "hadoofus_crc32c.h"]
+WIREV_LIB = os.path.join(LIBDIR, "libhadoofus_wirev.so")
+WIREV_SOURCES = ["wirev_kernels.hip", "writev_kernels.hip", "wirev.cpp"]
+WIREV_HEADERS = ["wirev_internal.h", "wire_internal.h", "wire_frame.h", "wire_layout.h", "writev_internal.h",
+                 "writev_layout.h", "companion_support.h", "crc32c_outpkt.h", "crc32c_tables.h", "wirev_exports.map"]
+WIREV_PUBLIC = ["hadoofus_wirev.h", "hadoofus_writev.h", "hadoofus_crc32c.h"]
 ARCH = os.environ.get("HADOOFUS_OFFLOAD_ARCH", "gfx950")
 
 
@@ -96,8 +104,8 @@ def _companion_cmd(out, sources, exports):
 
 def build(force=False, verbose=False, diag=True):
     """Build the release library (and, with diag=True, the diagnostic one,
-    in parallel), then the MD5CRC, gather-write, wire-stream and wire-batch
-    companions (in parallel).
+    in parallel), then the MD5CRC, gather-write, wire-stream, wire-batch and
+    gather-wire companions (in parallel).
     Returns the release library's path."""
     os.makedirs(LIBDIR, exist_ok=True)
     jobs = []
@@ -120,7 +128,8 @@ def build(force=False, verbose=False, diag=True):
             (MD5CRC_LIB, MD5CRC_SOURCES, MD5CRC_HEADERS, MD5CRC_PUBLIC, "md5crc_exports.map"),
             (WRITEV_LIB, WRITEV_SOURCES, WRITEV_HEADERS, WRITEV_PUBLIC, "writev_exports.map"),
             (WIRE_LIB, WIRE_SOURCES, WIRE_HEADERS, WIRE_PUBLIC, "wire_exports.map"),
-            (WIRE_BATCH_LIB, WIRE_BATCH_SOURCES, WIRE_BATCH_HEADERS, WIRE_BATCH_PUBLIC, "wire_batch_exports.map")):
+            (WIRE_BATCH_LIB, WIRE_BATCH_SOURCES, WIRE_BATCH_HEADERS, WIRE_BATCH_PUBLIC, "wire_batch_exports.map"),
+            (WIREV_LIB, WIREV_SOURCES, WIREV_HEADERS, WIREV_PUBLIC, "wirev_exports.map")):
         if force or _stale(out, sources, headers, public, [LIB]):
             cmd = _companion_cmd(out + ".tmp", sources, exports)
             if verbose:

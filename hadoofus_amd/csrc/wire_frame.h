@@ -1,7 +1,9 @@
 // One packet of a write framed into its wire stream on gfx950: the body that
 // frame_packets_kernel (wire_kernels.hip, one write per launch) and
 // frame_batch_kernel (wire_batch_kernels.hip, a batch of writes per launch)
-// both run, so there is one definition of it.  Device code; hipcc only.
+// both run, so there is one definition of it.  frame_gather_kernel
+// (wirev_kernels.hip, the data in a list of fragments) runs its region copy
+// and its CRC-and-header part.  Device code; hipcc only.
 //
 // A packet is three regions of the stream, each starting and ending at any
 // byte address (a full packet's stride is odd): the header, which the
@@ -148,6 +150,20 @@ WIRE_DEV void copy_header(const uint32_t *lh, uintptr_t d, uint32_t hb, uint32_t
   }
 }
 
+// What slice 0 alone does for packet p of write w, whose first byte lies at
+// h0: the CRC region from the plan's array, then the header, composed into
+// the workgroup's 8 words of LDS at lh.  A whole workgroup of 256 threads.
+template <bool SC1>
+WIRE_DEV void frame_crcs_and_header(const Write &w, const Pkt &p, uintptr_t h0, uint32_t *lh, uint32_t tid) {
+  const uintptr_t c0 = h0 + w.hb, d0 = c0 + 4u * uintptr_t(p.ncrc);
+  if (p.ncrc) copy_region<SC1>((gbytes)(w.crc + p.cidx), c0, d0, true, 0u, 1u, tid);
+  if (tid == 0)
+    hdfs_crc32c::outpkt::put_out_header(reinterpret_cast<uint8_t *>(lh), int(w.proto), p.off, p.seq, p.last != 0u,
+                                        int32_t(p.dlen), p.ncrc);
+  __syncthreads();
+  copy_header<SC1>(lh, h0, w.hb, tid);
+}
+
 // Slice `slice` of `slices` of packet i (i < w.npk) of write w, by a whole
 // workgroup of 256 threads; lh: 8 words of LDS of the workgroup.  Every
 // argument but tid is uniform across the workgroup.
@@ -155,15 +171,10 @@ template <bool SC1>
 WIRE_DEV void frame_packet(const Write &w, uint32_t i, uint32_t slice, uint32_t slices, uint32_t *lh, uint32_t tid) {
   const Pkt p = packet_at(w, i);
   const uintptr_t h0 = reinterpret_cast<uintptr_t>(w.wire) + p.wire_off;
-  const uintptr_t c0 = h0 + w.hb, d0 = c0 + 4u * uintptr_t(p.ncrc), d1 = d0 + p.dlen;
+  const uintptr_t d0 = h0 + w.hb + 4u * uintptr_t(p.ncrc), d1 = d0 + p.dlen;
   copy_region<SC1>((gbytes)(w.data + p.data_off), d0, d1, slice == 0u, slice, slices, tid);
   if (slice != 0u) return;
-  if (p.ncrc) copy_region<SC1>((gbytes)(w.crc + p.cidx), c0, d0, true, 0u, 1u, tid);
-  if (tid == 0)
-    hdfs_crc32c::outpkt::put_out_header(reinterpret_cast<uint8_t *>(lh), int(w.proto), p.off, p.seq, p.last != 0u,
-                                        int32_t(p.dlen), p.ncrc);
-  __syncthreads();
-  copy_header<SC1>(lh, h0, w.hb, tid);
+  frame_crcs_and_header<SC1>(w, p, h0, lh, tid);
 }
 
 }  // namespace frame

@@ -13,9 +13,9 @@
 
 #include "companion_support.h"
 #include "crc32c_outpkt.h"
-#include "crc32c_tables.h"
 #include "hadoofus_writev.h"
 #include "writev_internal.h"
+#include "writev_layout.h"
 
 namespace hdfs_writev {
 namespace {
@@ -23,100 +23,12 @@ namespace {
 using namespace hdfs_companion;
 using namespace hdfs_crc32c::outpkt;
 
-// A run of whole chunks inside one fragment shorter than this is not worth a
-// segment-table entry: its chunks join the gathered set.  8 chunks are one
-// tile of the main library's tiled kernel; a shorter run would be a ragged
-// tile there, filled to less than its width, for the price of a table entry.
-constexpr uint32_t kMinSegChunks = 8;
 constexpr uint64_t kHostWindow = uint64_t(64) << 20;  // host fragments: bytes packed per call of the main library
 
-// ---- layout -----------------------------------------------------------------
-// A run of whole chunks [chunk0, chunk0 + ...) inside fragment `frag`.
-struct Run {
-  int frag;
-  uint64_t at;      // byte offset of the run in the fragment
-  uint64_t len;     // bytes (the write's partial last chunk included)
-  uint64_t chunk0;  // first chunk: its place in the CRC array
-  uint64_t chunk1;  // one past the last
-};
-
-struct Layout {
-  hdfs_writev_layout_info info;
-  uint64_t n0 = 0;  // bytes of the short first chunk (0: the write starts on the grid)
-  std::vector<Run> runs;
-  std::vector<GChunk> chunks;  // filled only when bases are given
-  std::vector<Piece> pieces;
-};
-
-// The chunk grid is hdfs_crc32c_compose_packets': a short first chunk that
-// completes the block offset's chunk, then 512-B chunks, the last one possibly
-// partial.  bases == NULL: counts only.
-int build_layout(const uint64_t *lens, const void *const *bases, int n, int64_t off, Layout &L) {
-  L = Layout{};
-  hdfs_writev_layout_info &I = L.info;
-  std::memset(&I, 0, sizeof(I));
-  I.min_seg_chunks = kMinSegChunks;
-  uint64_t total = 0;
-  for (int f = 0; f < n; f++) {
-    if (lens[f] > (uint64_t(1) << 62) - total) return fail(HDFS_CRC32C_EINVAL, "fragment %d: the write's length overflows", f);
-    total += lens[f];
-  }
-  const uint64_t cs = kWriteChunk;
-  const uint64_t n0 = (total && off % int64_t(cs)) ? std::min<uint64_t>(total, cs - uint64_t(off % int64_t(cs))) : 0;
-  const uint64_t k0 = n0 ? 1 : 0;
-  const uint64_t nchunks = k0 + (total - n0 + cs - 1) / cs;
-  if (nchunks > 0xFFFFFFF0ull) return fail(HDFS_CRC32C_EINVAL, "more than 2^32 - 16 chunks in one write");
-  L.n0 = n0;
-  I.total = total;
-  I.nchunks = nchunks;
-  auto start = [&](uint64_t i) { return i < k0 ? 0 : n0 + (i - k0) * cs; };
-  auto end = [&](uint64_t i) { return std::min(start(i + 1), total); };
-  // runs of grid chunks wholly inside one fragment
-  uint64_t a = 0;
-  for (int f = 0; f < n; f++) {
-    if (!lens[f]) continue;
-    const uint64_t b = a + lens[f];
-    const uint64_t i0 = a <= n0 ? k0 : k0 + (a - n0 + cs - 1) / cs;               // first grid chunk starting at or after a
-    const uint64_t i1 = b == total ? nchunks : (b < n0 ? 0 : k0 + (b - n0) / cs);  // chunks ending at or before b
-    if (i1 > i0 && i1 - i0 >= kMinSegChunks) {
-      L.runs.push_back(Run{f, start(i0) - a, end(i1 - 1) - start(i0), i0, i1});
-      I.nsegments++;
-      I.seg_chunks += i1 - i0;
-    }
-    a = b;
-  }
-  // every other chunk is gathered from its pieces
-  I.ngathered = nchunks - I.seg_chunks;
-  if (bases) L.chunks.reserve(size_t(I.ngathered));
-  int f = 0;        // the first fragment that may reach into the chunk at hand
-  uint64_t fa = 0;  // its offset in the write
-  size_t ri = 0;
-  for (uint64_t i = 0; i < nchunks; i++) {
-    if (ri < L.runs.size() && i == L.runs[ri].chunk0) {
-      i = L.runs[ri++].chunk1 - 1;
-      continue;
-    }
-    const uint64_t s = start(i), e = end(i);
-    while (fa + lens[f] <= s) fa += lens[f++];  // s < total: ends inside the list
-    uint64_t pos = s, ga = fa;
-    uint32_t count = 0;
-    for (int g = f; pos < e; g++) {
-      const uint64_t ge = ga + lens[g];
-      if (ge > pos) {  // (a zero-length fragment has no piece)
-        const uint64_t take = std::min(e, ge) - pos;
-        if (bases) L.pieces.push_back(Piece{static_cast<const uint8_t *>(bases[g]) + (pos - ga), uint32_t(take), 0u});
-        pos += take;
-        count++;
-      }
-      ga = ge;
-    }
-    if (I.npieces + count > 0xFFFFFFF0ull) return fail(HDFS_CRC32C_EINVAL, "more than 2^32 - 16 pieces in one write");
-    if (bases) L.chunks.push_back(GChunk{uint32_t(i), uint32_t(I.npieces), count, 0u});
-    I.npieces += count;
-    I.max_pieces = std::max(I.max_pieces, count);
-  }
-  return HDFS_CRC32C_OK;
-}
+// The layout of a gather write (Run, Layout, build_layout, kMinSegChunks), the
+// slicing tables and the run that leaves the chunk CRCs in a device array
+// (gather_plan, enqueue_gather) are writev_layout.h's, shared with the
+// gather-wire library.
 
 // ---- device scratch -----------------------------------------------------------
 // The CRC array, the chunk and piece tables and the pinned landing area of one
@@ -147,14 +59,7 @@ struct Scratch : DeviceScratch {
     int rc = bind(to, "stream and tables", release_own);
     if (rc) return rc;
     if (!slice) {  // bound anew: the slicing tables
-      hipError_t e = hipMalloc(&slice, 2 * kSliceWords * sizeof(uint32_t));
-      if (e != hipSuccess) slice = nullptr;
-      if (e == hipSuccess) {
-        std::vector<uint32_t> t(2 * kSliceWords);
-        hdfs_crc32c::make_slicing4(reinterpret_cast<uint32_t(*)[256]>(t.data()), hdfs_crc32c::kPoly);
-        hdfs_crc32c::make_slicing4(reinterpret_cast<uint32_t(*)[256]>(t.data() + kSliceWords), hdfs_crc32c::kPolyZlib);
-        e = hipMemcpy(slice, t.data(), t.size() * sizeof(uint32_t), hipMemcpyHostToDevice);
-      }
+      const hipError_t e = upload_slicing_tables(&slice);
       if (e != hipSuccess) {
         unbind(release_own);
         return fail(HDFS_CRC32C_EHIP, "stream and tables: %s", hipGetErrorString(e));
@@ -207,37 +112,16 @@ int compose_device(const hdfs_crc32c_iovec *iov, const Layout &L, int dev, const
                    int proto, int ctype, uint8_t *hdr_out, hdfs_crc32c_out_packet *pkts) {
   const hdfs_writev_layout_info &I = L.info;
   const size_t crc_bytes = size_t(I.nchunks) * 4;
-  const size_t ch_bytes = size_t(I.ngathered) * sizeof(GChunk), pc_bytes = size_t(I.npieces) * sizeof(Piece);
   DeviceGuard g(dev);
   std::lock_guard<std::mutex> lk(g_mu);
-  int rc = g_s.reserve(dev, crc_bytes, ch_bytes + pc_bytes);
+  int rc = g_s.reserve(dev, crc_bytes, gather_table_bytes(L));
   if (rc) return rc;
   uint32_t *d_crc = g_s.crc.as<uint32_t>();
-  GChunk *d_ch = g_s.tab.as<GChunk>();
-  Piece *d_pc = reinterpret_cast<Piece *>(g_s.tab.as<uint8_t>() + ch_bytes);
-  const bool zlib = ctype == HDFS_CRC32C_CSUM_CRC32;
-  // in place: every run is one segment of one compute plan, its CRCs at the
-  // run's place in the write's CRC array
   hdfs_crc32c_plan *cplan = nullptr;
-  if (!L.runs.empty()) {
-    std::vector<hdfs_crc32c_segment> segs(L.runs.size());
-    for (size_t i = 0; i < segs.size(); i++) {
-      const Run &r = L.runs[i];
-      segs[i] = hdfs_crc32c_segment{static_cast<const uint8_t *>(iov[r.frag].base) + r.at, r.len, kWriteChunk,
-                                    HDFS_CRC32C_SEG_BE | (zlib ? HDFS_CRC32C_SEG_CRC32 : 0u), 0u, 0u,
-                                    d_crc + r.chunk0, nullptr};
-    }
-    if ((rc = hdfs_crc32c_plan_create(&cplan, HDFS_CRC32C_MODE_COMPUTE, segs.data(), segs.size())))
-      return engine_fail(rc, "compute plan");
-  }
+  if ((rc = gather_plan(iov, L, ctype, d_crc, &cplan))) return rc;
   hipStream_t st = g_s.st;
   hipError_t e = hipSuccess;
-  if (ch_bytes) e = hipMemcpyAsync(d_ch, L.chunks.data(), ch_bytes, hipMemcpyHostToDevice, st);
-  if (e == hipSuccess && pc_bytes) e = hipMemcpyAsync(d_pc, L.pieces.data(), pc_bytes, hipMemcpyHostToDevice, st);
-  if (e == hipSuccess && cplan && (rc = hdfs_crc32c_plan_execute(cplan, st))) rc = engine_fail(rc, "compute plan");
-  if (e == hipSuccess && !rc)
-    e = launch_gather_chunks(d_ch, uint32_t(I.ngathered), d_pc, uint32_t(I.npieces), g_s.slice + (zlib ? kSliceWords : 0),
-                             d_crc, uint32_t(I.nchunks), st);
+  rc = enqueue_gather(L, cplan, ctype, g_s.tab.p, g_s.slice, d_crc, st, &e);
   if (e == hipSuccess && !rc) e = hipMemcpyAsync(g_s.h_crc.p, d_crc, crc_bytes, hipMemcpyDeviceToHost, st);
   // always: the tables and the CRC array must be out of use before the lock goes
   if ((rc = sync_and_report(st, e, rc, cplan, "gather write"))) return rc;
