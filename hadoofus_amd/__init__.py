@@ -15,7 +15,9 @@ libhadoofus_wire.so, loaded the same way (wire.py); the streams of a batch of
 writes in one call (include/hadoofus_wire_batch.h) in
 libhadoofus_wire_batch.so (wire_batch.py); a write held in a list of device
 buffers as one such stream (include/hadoofus_wirev.h) in libhadoofus_wirev.so
-(wirev.py).
+(wirev.py); a write's stream made in one pass, the chunk CRCs computed by the
+framing kernel (include/hadoofus_wire_fused.h), in libhadoofus_wire_fused.so
+(wire_fused.py).
 """
 from .abi import (  # noqa: F401
     LIB_PATH, bind_product, bind_diag, CSUM_NULL, CSUM_CRC32, CSUM_CRC32C, ERR_BAD_CHECKSUM, ERR_CRC_LEN,
@@ -34,5 +36,6 @@ from .writev import compose_packets_iov, layout as writev_layout  # noqa: F401  
 from .wire import compose_wire, layout as wire_layout  # noqa: F401  (binds nothing until first use)
 from .wire_batch import compose_wire_batch, layout as wire_batch_layout  # noqa: F401  (binds nothing until first use)
 from .wirev import compose_wire as compose_wire_iov, layout as wirev_layout  # noqa: F401  (binds nothing until first use)
+from .wire_fused import compose_wire as compose_wire_fused  # noqa: F401  (binds nothing until first use)
 
 __all__ = [n for n in dir() if not n.startswith("_")]

@@ -11,18 +11,21 @@ tools/ experiments and bench.py's ceiling measurement load it; the product
 library contains none of that code and reads no tuning knob from the
 environment.
 
-Five companion libraries link against the release library and are built
+Six companion libraries link against the release library and are built
 after it: libhadoofus_md5crc.so (include/hadoofus_md5crc.h),
 libhadoofus_writev.so (include/hadoofus_writev.h), libhadoofus_wire.so
 (include/hadoofus_wire.h), libhadoofus_wire_batch.so
-(include/hadoofus_wire_batch.h) and libhadoofus_wirev.so
-(include/hadoofus_wirev.h), each with its own sources and export map.
-All five share the host support of companion_support.h (last error, the
+(include/hadoofus_wire_batch.h), libhadoofus_wirev.so
+(include/hadoofus_wirev.h) and libhadoofus_wire_fused.so
+(include/hadoofus_wire_fused.h), each with its own sources and export map.
+All six share the host support of companion_support.h (last error, the
 engine's device, grow-only buffers, scratch bound to a device, pointer
 placement, the end of a call); the wire libraries also share the framing and
 layout code of wire_frame.h and wire_layout.h, and the gather libraries
 (writev, wirev) the gather layout of writev_layout.h and the kernel of
-writev_kernels.hip.  These files are compiled into every library that uses
+writev_kernels.hip.  The fused wire library uses the layout code of
+wire_layout.h with a kernel and CRC tables of its own (wire_fused_crc.h,
+wire_fused_tables.h).  These files are compiled into every library that uses
 them, each keeping its own copy; no companion links another.
 """
 import os
@@ -65,6 +68,12 @@ WIREV_SOURCES = ["wirev_kernels.hip", "writev_kernels.hip", "wirev.cpp"]
 WIREV_HEADERS = ["wirev_internal.h", "wire_internal.h", "wire_frame.h", "wire_layout.h", "writev_internal.h",
                  "writev_layout.h", "companion_support.h", "crc32c_outpkt.h", "crc32c_tables.h", "wirev_exports.map"]
 WIREV_PUBLIC = ["hadoofus_wirev.h", "hadoofus_writev.h", "hadoofus_crc32c.h"]
+WIRE_FUSED_LIB = os.path.join(LIBDIR, "libhadoofus_wire_fused.so")
+WIRE_FUSED_SOURCES = ["wire_fused_kernels.hip", "wire_fused.cpp"]
+WIRE_FUSED_HEADERS = ["wire_fused_internal.h", "wire_fused_crc.h", "wire_fused_tables.h", "wire_internal.h",
+                      "wire_layout.h", "companion_support.h", "crc32c_outpkt.h", "crc32c_tables.h",
+                      "wire_fused_exports.map"]
+WIRE_FUSED_PUBLIC = ["hadoofus_wire_fused.h", "hadoofus_crc32c.h"]
 ARCH = os.environ.get("HADOOFUS_OFFLOAD_ARCH", "gfx950")
 
 
@@ -104,8 +113,8 @@ def _companion_cmd(out, sources, exports):
 
 def build(force=False, verbose=False, diag=True):
     """Build the release library (and, with diag=True, the diagnostic one,
-    in parallel), then the MD5CRC, gather-write, wire-stream, wire-batch and
-    gather-wire companions (in parallel).
+    in parallel), then the MD5CRC, gather-write, wire-stream, wire-batch,
+    gather-wire and fused-wire companions (in parallel).
     Returns the release library's path."""
     os.makedirs(LIBDIR, exist_ok=True)
     jobs = []
@@ -129,7 +138,8 @@ def build(force=False, verbose=False, diag=True):
             (WRITEV_LIB, WRITEV_SOURCES, WRITEV_HEADERS, WRITEV_PUBLIC, "writev_exports.map"),
             (WIRE_LIB, WIRE_SOURCES, WIRE_HEADERS, WIRE_PUBLIC, "wire_exports.map"),
             (WIRE_BATCH_LIB, WIRE_BATCH_SOURCES, WIRE_BATCH_HEADERS, WIRE_BATCH_PUBLIC, "wire_batch_exports.map"),
-            (WIREV_LIB, WIREV_SOURCES, WIREV_HEADERS, WIREV_PUBLIC, "wirev_exports.map")):
+            (WIREV_LIB, WIREV_SOURCES, WIREV_HEADERS, WIREV_PUBLIC, "wirev_exports.map"),
+            (WIRE_FUSED_LIB, WIRE_FUSED_SOURCES, WIRE_FUSED_HEADERS, WIRE_FUSED_PUBLIC, "wire_fused_exports.map")):
         if force or _stale(out, sources, headers, public, [LIB]):
             cmd = _companion_cmd(out + ".tmp", sources, exports)
             if verbose:
