@@ -17,7 +17,9 @@ libhadoofus_wire_batch.so (wire_batch.py); a write held in a list of device
 buffers as one such stream (include/hadoofus_wirev.h) in libhadoofus_wirev.so
 (wirev.py); a write's stream made in one pass, the chunk CRCs computed by the
 framing kernel (include/hadoofus_wire_fused.h), in libhadoofus_wire_fused.so
-(wire_fused.py).
+(wire_fused.py); the streams of a batch of writes made that way in one launch
+(include/hadoofus_wire_fused_batch.h) in libhadoofus_wire_fused_batch.so
+(wire_fused_batch.py).
 """
 from .abi import (  # noqa: F401
     LIB_PATH, bind_product, bind_diag, CSUM_NULL, CSUM_CRC32, CSUM_CRC32C, ERR_BAD_CHECKSUM, ERR_CRC_LEN,
@@ -37,5 +39,6 @@ from .wire import compose_wire, layout as wire_layout  # noqa: F401  (binds noth
 from .wire_batch import compose_wire_batch, layout as wire_batch_layout  # noqa: F401  (binds nothing until first use)
 from .wirev import compose_wire as compose_wire_iov, layout as wirev_layout  # noqa: F401  (binds nothing until first use)
 from .wire_fused import compose_wire as compose_wire_fused  # noqa: F401  (binds nothing until first use)
+from .wire_fused_batch import compose as compose_wire_fused_batch  # noqa: F401  (binds nothing until first use)
 
 __all__ = [n for n in dir() if not n.startswith("_")]

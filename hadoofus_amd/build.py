@@ -27,6 +27,12 @@ writev_kernels.hip.  The fused wire library uses the layout code of
 wire_layout.h with a kernel and CRC tables of its own (wire_fused_crc.h,
 wire_fused_tables.h).  These files are compiled into every library that uses
 them, each keeping its own copy; no companion links another.
+
+A seventh companion, libhadoofus_wire_fused_batch.so
+(include/hadoofus_wire_fused_batch.h), is built the same way from its own
+sources and export map: the fused kernel's round (wire_fused_round.h, compiled
+into it and into the fused wire library) over the packets of a batch of
+writes, with the lookup of wire_fused_batch_lookup.h.
 """
 import os
 import subprocess
@@ -70,10 +76,17 @@ WIREV_HEADERS = ["wirev_internal.h", "wire_internal.h", "wire_frame.h", "wire_la
 WIREV_PUBLIC = ["hadoofus_wirev.h", "hadoofus_writev.h", "hadoofus_crc32c.h"]
 WIRE_FUSED_LIB = os.path.join(LIBDIR, "libhadoofus_wire_fused.so")
 WIRE_FUSED_SOURCES = ["wire_fused_kernels.hip", "wire_fused.cpp"]
-WIRE_FUSED_HEADERS = ["wire_fused_internal.h", "wire_fused_crc.h", "wire_fused_tables.h", "wire_internal.h",
-                      "wire_layout.h", "companion_support.h", "crc32c_outpkt.h", "crc32c_tables.h",
+WIRE_FUSED_HEADERS = ["wire_fused_internal.h", "wire_fused_round.h", "wire_fused_crc.h", "wire_fused_tables.h",
+                      "wire_internal.h", "wire_layout.h", "companion_support.h", "crc32c_outpkt.h", "crc32c_tables.h",
                       "wire_fused_exports.map"]
 WIRE_FUSED_PUBLIC = ["hadoofus_wire_fused.h", "hadoofus_crc32c.h"]
+WIRE_FUSED_BATCH_LIB = os.path.join(LIBDIR, "libhadoofus_wire_fused_batch.so")
+WIRE_FUSED_BATCH_SOURCES = ["wire_fused_batch_kernels.hip", "wire_fused_batch.cpp"]
+WIRE_FUSED_BATCH_HEADERS = ["wire_fused_batch_internal.h", "wire_fused_batch_lookup.h", "wire_fused_round.h",
+                            "wire_fused_crc.h", "wire_fused_tables.h", "wire_internal.h", "wire_layout.h",
+                            "companion_support.h", "crc32c_outpkt.h", "crc32c_tables.h",
+                            "wire_fused_batch_exports.map"]
+WIRE_FUSED_BATCH_PUBLIC = ["hadoofus_wire_fused_batch.h", "hadoofus_crc32c.h"]
 ARCH = os.environ.get("HADOOFUS_OFFLOAD_ARCH", "gfx950")
 
 
@@ -114,7 +127,7 @@ def _companion_cmd(out, sources, exports):
 def build(force=False, verbose=False, diag=True):
     """Build the release library (and, with diag=True, the diagnostic one,
     in parallel), then the MD5CRC, gather-write, wire-stream, wire-batch,
-    gather-wire and fused-wire companions (in parallel).
+    gather-wire, fused-wire and fused-wire-batch companions (in parallel).
     Returns the release library's path."""
     os.makedirs(LIBDIR, exist_ok=True)
     jobs = []
@@ -139,7 +152,9 @@ def build(force=False, verbose=False, diag=True):
             (WIRE_LIB, WIRE_SOURCES, WIRE_HEADERS, WIRE_PUBLIC, "wire_exports.map"),
             (WIRE_BATCH_LIB, WIRE_BATCH_SOURCES, WIRE_BATCH_HEADERS, WIRE_BATCH_PUBLIC, "wire_batch_exports.map"),
             (WIREV_LIB, WIREV_SOURCES, WIREV_HEADERS, WIREV_PUBLIC, "wirev_exports.map"),
-            (WIRE_FUSED_LIB, WIRE_FUSED_SOURCES, WIRE_FUSED_HEADERS, WIRE_FUSED_PUBLIC, "wire_fused_exports.map")):
+            (WIRE_FUSED_LIB, WIRE_FUSED_SOURCES, WIRE_FUSED_HEADERS, WIRE_FUSED_PUBLIC, "wire_fused_exports.map"),
+            (WIRE_FUSED_BATCH_LIB, WIRE_FUSED_BATCH_SOURCES, WIRE_FUSED_BATCH_HEADERS, WIRE_FUSED_BATCH_PUBLIC,
+             "wire_fused_batch_exports.map")):
         if force or _stale(out, sources, headers, public, [LIB]):
             cmd = _companion_cmd(out + ".tmp", sources, exports)
             if verbose:
