@@ -19,7 +19,9 @@ buffers as one such stream (include/hadoofus_wirev.h) in libhadoofus_wirev.so
 framing kernel (include/hadoofus_wire_fused.h), in libhadoofus_wire_fused.so
 (wire_fused.py); the streams of a batch of writes made that way in one launch
 (include/hadoofus_wire_fused_batch.h) in libhadoofus_wire_fused_batch.so
-(wire_fused_batch.py).
+(wire_fused_batch.py); a write held in a list of device buffers made that way
+(include/hadoofus_wirev_fused.h) in libhadoofus_wirev_fused.so
+(wirev_fused.py).
 """
 from .abi import (  # noqa: F401
     LIB_PATH, bind_product, bind_diag, CSUM_NULL, CSUM_CRC32, CSUM_CRC32C, ERR_BAD_CHECKSUM, ERR_CRC_LEN,
@@ -40,5 +42,6 @@ from .wire_batch import compose_wire_batch, layout as wire_batch_layout  # noqa:
 from .wirev import compose_wire as compose_wire_iov, layout as wirev_layout  # noqa: F401  (binds nothing until first use)
 from .wire_fused import compose_wire as compose_wire_fused  # noqa: F401  (binds nothing until first use)
 from .wire_fused_batch import compose as compose_wire_fused_batch  # noqa: F401  (binds nothing until first use)
+from .wirev_fused import compose_wirev_fused, layout as wirev_fused_layout  # noqa: F401  (binds nothing until first use)
 
 __all__ = [n for n in dir() if not n.startswith("_")]

@@ -33,6 +33,13 @@ A seventh companion, libhadoofus_wire_fused_batch.so
 sources and export map: the fused kernel's round (wire_fused_round.h, compiled
 into it and into the fused wire library) over the packets of a batch of
 writes, with the lookup of wire_fused_batch_lookup.h.
+
+An eighth companion, libhadoofus_wirev_fused.so
+(include/hadoofus_wirev_fused.h), is built the same way from its own sources
+and export map: the same round over the packets of a write held in device
+fragments, found through a fragment table with the lookup of
+wirev_fused_lookup.h.  It compiles neither the gather layout nor the gather
+kernel of the gather libraries.
 """
 import os
 import subprocess
@@ -87,6 +94,12 @@ WIRE_FUSED_BATCH_HEADERS = ["wire_fused_batch_internal.h", "wire_fused_batch_loo
                             "companion_support.h", "crc32c_outpkt.h", "crc32c_tables.h",
                             "wire_fused_batch_exports.map"]
 WIRE_FUSED_BATCH_PUBLIC = ["hadoofus_wire_fused_batch.h", "hadoofus_crc32c.h"]
+WIREV_FUSED_LIB = os.path.join(LIBDIR, "libhadoofus_wirev_fused.so")
+WIREV_FUSED_SOURCES = ["wirev_fused_kernels.hip", "wirev_fused.cpp"]
+WIREV_FUSED_HEADERS = ["wirev_fused_internal.h", "wirev_fused_lookup.h", "wire_fused_round.h", "wire_fused_crc.h",
+                       "wire_fused_tables.h", "wire_internal.h", "wire_layout.h", "companion_support.h",
+                       "crc32c_outpkt.h", "crc32c_tables.h", "wirev_fused_exports.map"]
+WIREV_FUSED_PUBLIC = ["hadoofus_wirev_fused.h", "hadoofus_crc32c.h"]
 ARCH = os.environ.get("HADOOFUS_OFFLOAD_ARCH", "gfx950")
 
 
@@ -127,7 +140,8 @@ def _companion_cmd(out, sources, exports):
 def build(force=False, verbose=False, diag=True):
     """Build the release library (and, with diag=True, the diagnostic one,
     in parallel), then the MD5CRC, gather-write, wire-stream, wire-batch,
-    gather-wire, fused-wire and fused-wire-batch companions (in parallel).
+    gather-wire, fused-wire, fused-wire-batch and fused-gather-wire companions
+    (in parallel).
     Returns the release library's path."""
     os.makedirs(LIBDIR, exist_ok=True)
     jobs = []
@@ -154,7 +168,9 @@ def build(force=False, verbose=False, diag=True):
             (WIREV_LIB, WIREV_SOURCES, WIREV_HEADERS, WIREV_PUBLIC, "wirev_exports.map"),
             (WIRE_FUSED_LIB, WIRE_FUSED_SOURCES, WIRE_FUSED_HEADERS, WIRE_FUSED_PUBLIC, "wire_fused_exports.map"),
             (WIRE_FUSED_BATCH_LIB, WIRE_FUSED_BATCH_SOURCES, WIRE_FUSED_BATCH_HEADERS, WIRE_FUSED_BATCH_PUBLIC,
-             "wire_fused_batch_exports.map")):
+             "wire_fused_batch_exports.map"),
+            (WIREV_FUSED_LIB, WIREV_FUSED_SOURCES, WIREV_FUSED_HEADERS, WIREV_FUSED_PUBLIC,
+             "wirev_fused_exports.map")):
         if force or _stale(out, sources, headers, public, [LIB]):
             cmd = _companion_cmd(out + ".tmp", sources, exports)
             if verbose:

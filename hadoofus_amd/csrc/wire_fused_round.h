@@ -5,6 +5,11 @@
 // two kernels differ only in how a workgroup finds its next packet and the
 // write it belongs to; everything below takes the packet as a Unit and never
 // sees a Write again: unit_of is the only place one is live.
+// frame_fused_gather_kernel (wirev_fused_kernels.hip, a write held in
+// fragments) runs the same round with a source of its own: it changes a
+// Unit's src, loads a round with a fragment boundary inside by its own code
+// into the registers load_round would have filled, and ends its ragged chunk
+// in ragged_finish.
 //
 // A wave's round of a packet is 4 KiB of the packet's full chunks: four
 // coalesced 16-B loads (load_round), the same registers stored straight out
@@ -192,20 +197,14 @@ FUSED_DEV void header(uint32_t *hdr, uint32_t proto, const Unit &u, uint32_t lan
   __builtin_amdgcn_wave_barrier();
 }
 
-// The packet's chunk shorter than 512 B (n bytes behind its full chunks, n =
-// 0: none), by one whole wave: copied, and its CRC stored.  src0: the packet's
-// first data byte in the write (wave 0's u.src; a kernel that has the write at
-// hand may say it in the form that costs it fewest registers).  Byte f of the
-// zero frame holds byte f - pad of the chunk; below pad the offset wraps out
-// of the range.
+// The second half of ragged_chunk, for a kernel that loads the chunk's bytes
+// its own way: b[j] is byte 8 lane + j of the zero frame (zero below pad).
+// The bytes are stored behind the packet's full chunks, and the chunk's CRC.
 template <bool CSUM>
-FUSED_DEV void ragged_chunk(const uint32_t *img, const uint32_t *tab, uintptr_t src0, const Unit &u, uint32_t lane) {
+FUSED_DEV void ragged_finish(const uint32_t *img, const uint32_t *tab, const uint32_t (&b)[8], const Unit &u,
+                             uint32_t lane) {
   const uint32_t nfull = u.p.dlen / kChunk, n = u.p.dlen % kChunk, pad = kChunk - n;
-  const __amdgpu_buffer_rsrc_t rs = range_of(src0 + uintptr_t(kChunk) * nfull, n);
   const __amdgpu_buffer_rsrc_t rd = range_of(u.d0 + uintptr_t(kChunk) * nfull, n);
-  uint32_t b[8];
-#pragma unroll
-  for (uint32_t j = 0; j < 8; j++) b[j] = load8(rs, 8u * lane + j - pad);
 #pragma unroll
   for (uint32_t j = 0; j < 8; j++) store8(rd, 8u * lane + j - pad, b[j]);
   if (!CSUM) return;
@@ -224,6 +223,22 @@ FUSED_DEV void ragged_chunk(const uint32_t *img, const uint32_t *tab, uintptr_t 
     val = crc::chunk_final(fold8(crc::piece_shift(img, i, crc::piece_raw(img, lane, x))), tab[crc::kCompactInit + n]);
   }
   store32(range_of(u.c0 + 4u * uintptr_t(nfull), n ? 4u : 0u), lane == 0u ? 0u : kNowhere, val);
+}
+
+// The packet's chunk shorter than 512 B (n bytes behind its full chunks, n =
+// 0: none), by one whole wave: copied, and its CRC stored.  src0: the packet's
+// first data byte in the write (wave 0's u.src; a kernel that has the write at
+// hand may say it in the form that costs it fewest registers).  Byte f of the
+// zero frame holds byte f - pad of the chunk; below pad the offset wraps out
+// of the range.
+template <bool CSUM>
+FUSED_DEV void ragged_chunk(const uint32_t *img, const uint32_t *tab, uintptr_t src0, const Unit &u, uint32_t lane) {
+  const uint32_t nfull = u.p.dlen / kChunk, n = u.p.dlen % kChunk, pad = kChunk - n;
+  const __amdgpu_buffer_rsrc_t rs = range_of(src0 + uintptr_t(kChunk) * nfull, n);
+  uint32_t b[8];
+#pragma unroll
+  for (uint32_t j = 0; j < 8; j++) b[j] = load8(rs, 8u * lane + j - pad);
+  ragged_finish<CSUM>(img, tab, b, u, lane);
 }
 
 // The workgroup's table image (wire_fused_crc.h) from the compact tables at
