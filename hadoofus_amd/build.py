@@ -74,7 +74,7 @@ WIRE_PUBLIC = ["hadoofus_wire.h", "hadoofus_crc32c.h"]
 WIRE_BATCH_LIB = os.path.join(LIBDIR, "libhadoofus_wire_batch.so")
 WIRE_BATCH_SOURCES = ["wire_batch_kernels.hip", "wire_batch.cpp"]
 WIRE_BATCH_HEADERS = ["wire_batch_internal.h", "wire_internal.h", "wire_frame.h", "wire_layout.h",
-                      "companion_support.h", "crc32c_outpkt.h", "wire_batch_exports.map"]
+                      "wire_batch_layout.h", "companion_support.h", "crc32c_outpkt.h", "wire_batch_exports.map"]
 WIRE_BATCH_PUBLIC = ["hadoofus_wire_batch.h", "hadoofus_crc32c.h"]
 WIREV_LIB = os.path.join(LIBDIR, "libhadoofus_wirev.so")
 WIREV_SOURCES = ["wirev_kernels.hip", "writev_kernels.hip", "wirev.cpp"]
@@ -84,21 +84,21 @@ WIREV_PUBLIC = ["hadoofus_wirev.h", "hadoofus_writev.h", "hadoofus_crc32c.h"]
 WIRE_FUSED_LIB = os.path.join(LIBDIR, "libhadoofus_wire_fused.so")
 WIRE_FUSED_SOURCES = ["wire_fused_kernels.hip", "wire_fused.cpp"]
 WIRE_FUSED_HEADERS = ["wire_fused_internal.h", "wire_fused_round.h", "wire_fused_crc.h", "wire_fused_tables.h",
-                      "wire_internal.h", "wire_layout.h", "companion_support.h", "crc32c_outpkt.h", "crc32c_tables.h",
+                      "wire_fused_host.h", "wire_internal.h", "wire_layout.h", "companion_support.h", "crc32c_outpkt.h", "crc32c_tables.h",
                       "wire_fused_exports.map"]
 WIRE_FUSED_PUBLIC = ["hadoofus_wire_fused.h", "hadoofus_crc32c.h"]
 WIRE_FUSED_BATCH_LIB = os.path.join(LIBDIR, "libhadoofus_wire_fused_batch.so")
 WIRE_FUSED_BATCH_SOURCES = ["wire_fused_batch_kernels.hip", "wire_fused_batch.cpp"]
 WIRE_FUSED_BATCH_HEADERS = ["wire_fused_batch_internal.h", "wire_fused_batch_lookup.h", "wire_fused_round.h",
-                            "wire_fused_crc.h", "wire_fused_tables.h", "wire_internal.h", "wire_layout.h",
-                            "companion_support.h", "crc32c_outpkt.h", "crc32c_tables.h",
+                            "wire_fused_crc.h", "wire_fused_tables.h", "wire_fused_host.h", "wire_internal.h",
+                            "wire_layout.h", "wire_batch_layout.h", "companion_support.h", "crc32c_outpkt.h", "crc32c_tables.h",
                             "wire_fused_batch_exports.map"]
 WIRE_FUSED_BATCH_PUBLIC = ["hadoofus_wire_fused_batch.h", "hadoofus_crc32c.h"]
 WIREV_FUSED_LIB = os.path.join(LIBDIR, "libhadoofus_wirev_fused.so")
 WIREV_FUSED_SOURCES = ["wirev_fused_kernels.hip", "wirev_fused.cpp"]
 WIREV_FUSED_HEADERS = ["wirev_fused_internal.h", "wirev_fused_lookup.h", "wire_fused_round.h", "wire_fused_crc.h",
-                       "wire_fused_tables.h", "wire_internal.h", "wire_layout.h", "companion_support.h",
-                       "crc32c_outpkt.h", "crc32c_tables.h", "wirev_fused_exports.map"]
+                       "wire_fused_tables.h", "wire_fused_host.h", "wire_internal.h", "wire_layout.h",
+                       "companion_support.h", "crc32c_outpkt.h", "crc32c_tables.h", "wirev_fused_exports.map"]
 WIREV_FUSED_PUBLIC = ["hadoofus_wirev_fused.h", "hadoofus_crc32c.h"]
 ARCH = os.environ.get("HADOOFUS_OFFLOAD_ARCH", "gfx950")
 

@@ -1,10 +1,12 @@
-// Host support shared by the companion libraries of libhadoofus_crc32c.so
-// (md5crc.cpp, writev.cpp, wire.cpp, wire_batch.cpp): the last-error text, the
-// engine's device, grow-only buffers, scratch bound to a device, where a
-// pointer lives, the packet argument check and the "always synchronise, then
-// report" tail of a call.  Host only: no kernel file includes it.  Every
-// library's export map keeps all of this local, so each library has its own
-// copy, its own last-error text included.
+// Host support shared by the eight companion libraries of
+// libhadoofus_crc32c.so (md5crc.cpp, writev.cpp and the six wire-stream
+// libraries wire*.cpp): the last-error text, the engine's device, grow-only
+// buffers, a device table with its pinned staging twin, scratch bound to a
+// device with the two events of a timing call, where a pointer lives, the
+// packet argument check and the "always synchronise, then report" tail of a
+// call.  Host only: no kernel file includes it.  Every library's export map
+// keeps all of this local, so each library has its own copy, its own
+// last-error text included.
 #ifndef HADOOFUS_COMPANION_SUPPORT_H
 #define HADOOFUS_COMPANION_SUPPORT_H
 
@@ -121,14 +123,37 @@ template <int (*Alloc)(void **, size_t) = pinned_alloc, void (*Free)(void *) = p
 using PinnedBuffer = GrowOnly<Alloc, Free>;
 
 constexpr size_t kScratchFloor = size_t(64) << 10;
+constexpr size_t kTableFloor = size_t(16) << 10;
+
+// A device table and its pinned staging twin, grown together: a call fills
+// pin and uploads it to dev.  A failure leaves both freed.
+struct TablePair {
+  DeviceBuffer dev;
+  PinnedBuffer<> pin;
+  int reserve(size_t bytes, size_t floor) {
+    if (bytes <= dev.cap) return HDFS_CRC32C_OK;
+    release();  // both go before either comes back
+    if (dev.reserve(bytes, floor) || pin.reserve(bytes, floor)) {
+      release();
+      return fail(HDFS_CRC32C_ENOMEM, "allocation of %zu table bytes failed", bytes < floor ? floor : bytes);
+    }
+    return HDFS_CRC32C_OK;
+  }
+  void release() {
+    dev.release();
+    pin.release();
+  }
+};
 
 // ---- scratch bound to a device ------------------------------------------------------
-// The base of a library's scratch: the device it was built on and a blocking
-// stream of its own (ordered after work queued earlier on the NULL stream).
-// The library adds its buffers and says how to free them.
+// The base of a library's scratch: the device it was built on, a blocking
+// stream of its own (ordered after work queued earlier on the NULL stream) and
+// the two events of a timing call.  The library adds its buffers and says how
+// to free them.
 struct DeviceScratch {
   int dev = -1;
   hipStream_t st = nullptr;
+  hipEvent_t ev[2] = {nullptr, nullptr};  // created when a timing call first runs
 
   // Bound to device `to` (the current one) afterwards.  When it was bound to
   // another device, everything is released there first.  `what` names the
@@ -149,14 +174,38 @@ struct DeviceScratch {
     return HDFS_CRC32C_OK;
   }
 
-  // Synchronise, free the library's buffers, then the stream: unbound.
+  // Synchronise, free the library's buffers, then the events and the stream:
+  // unbound.
   template <class ReleaseOwn>
   void unbind(ReleaseOwn &&release_own) {
     if (st) (void)hipStreamSynchronize(st);
     release_own();
+    destroy_events();
     if (st) (void)hipStreamDestroy(st);
     st = nullptr;
     dev = -1;
+  }
+
+  // Both events exist afterwards.  A failure keeps neither: the next call
+  // tries again.
+  int timing_events() {
+    if (ev[0]) return HDFS_CRC32C_OK;
+    hipError_t e = hipEventCreate(&ev[0]);
+    if (e != hipSuccess) ev[0] = nullptr;
+    if (e == hipSuccess && (e = hipEventCreate(&ev[1])) != hipSuccess) {
+      ev[1] = nullptr;
+      destroy_events();  // a lone first event would pass for the pair
+    }
+    if (e == hipSuccess) return HDFS_CRC32C_OK;
+    (void)hipGetLastError();
+    return fail(HDFS_CRC32C_EHIP, "events: %s", hipGetErrorString(e));
+  }
+
+  void destroy_events() {
+    for (hipEvent_t &e : ev) {
+      if (e) (void)hipEventDestroy(e);
+      e = nullptr;
+    }
   }
 };
 
@@ -234,6 +283,25 @@ struct Allocations {
     return rc;
   }
 };
+
+// Of a gather write: every non-empty fragment inside one allocation of device
+// `dev`, the stream inside one, and the stream clear of every fragment.
+inline int check_places(const hdfs_crc32c_iovec *iov, int n, const void *wire, uint64_t wire_len, int dev) {
+  int rc;
+  Allocations al;
+  const uintptr_t w0 = reinterpret_cast<uintptr_t>(wire), w1 = w0 + uintptr_t(wire_len);
+  for (int i = 0; i < n; i++) {
+    if (!iov[i].len) continue;
+    if ((rc = al.check(iov[i].base, iov[i].len, dev, "data"))) return prefix_fail(rc, "fragment %d", i);
+  }
+  if ((rc = al.check(wire, wire_len, dev, "wire"))) return rc;
+  for (int i = 0; i < n; i++) {
+    const uintptr_t a = reinterpret_cast<uintptr_t>(iov[i].base);
+    if (iov[i].len && a < w1 && w0 < a + uintptr_t(iov[i].len))
+      return fail(HDFS_CRC32C_EINVAL, "fragment %d and wire overlap", i);
+  }
+  return HDFS_CRC32C_OK;
+}
 
 // ---- the arguments of a packet run -----------------------------------------------------
 inline bool packet_args_ok(int proto, int ctype, int64_t offset_in_block) {

@@ -38,22 +38,10 @@ constexpr bool kSc1Stores = false;
 std::mutex g_mu;
 struct Scratch : DeviceScratch {
   DeviceBuffer crc;
-  hipEvent_t ev[2] = {nullptr, nullptr};  // of the timing call, created when it first runs
 
   int reserve(int to, size_t crc_bytes) {
-    const int rc = bind(to, "stream", [this] {
-      crc.release();
-      for (hipEvent_t &e : ev) {
-        if (e) (void)hipEventDestroy(e);
-        e = nullptr;
-      }
-    });
+    const int rc = bind(to, "stream", [this] { crc.release(); });
     return rc ? rc : crc.reserve(crc_bytes, kScratchFloor);
-  }
-  int timing_events() {
-    if (!ev[0] && (hipEventCreate(&ev[0]) != hipSuccess || hipEventCreate(&ev[1]) != hipSuccess))
-      return fail(HDFS_CRC32C_EHIP, "events: %s", hipGetErrorString(hipGetLastError()));
-    return HDFS_CRC32C_OK;
   }
 } g_s;
 

@@ -5,18 +5,20 @@
 // hdfs_crc32c_bound_device, its public API), the chunk CRCs of every write of
 // a batch come from one compute plan of that library, and both share one HIP
 // runtime.  The layout of a write and its records are wire_layout.h's, the
-// single-write library's own; this library's kernel (frame_batch_kernel) only
-// moves bytes, with wire_frame.h's code.
+// single-write library's own; a batch's front end (every entry's layout, the
+// argument checks, where the buffers may lie) is wire_batch_layout.h's, shared
+// with the fused batch library; this library's kernel (frame_batch_kernel)
+// only moves bytes, with wire_frame.h's code.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <cstring>
 #include <mutex>
 #include <vector>
 
 #include "crc32c_outpkt.h"
 #include "hadoofus_wire_batch.h"
 #include "wire_batch_internal.h"
+#include "wire_batch_layout.h"
 #include "wire_layout.h"
 
 namespace hdfs_wire {
@@ -26,58 +28,24 @@ static_assert(kBatchSlices == kSlices, "the batch kernel deals a packet as frame
 
 constexpr uint64_t kMaxPackets = 0x7FFFFFFFull / kBatchSlices;  // the grid: packets * 4 <= 2^31 - 1
 constexpr uint64_t kMaxChunks = 0xFFFFFFFFull - 15u;            // 2^32 - 16
-constexpr size_t kTableFloor = size_t(16) << 10;
-
-// The failure just recorded (by the shared layout code) was entry k's.
-int entry_fail(int rc, size_t k) { return prefix_fail(rc, "entry %zu", k); }
 
 // ---- layout of the batch ------------------------------------------------------------
-struct Batch {
-  std::vector<Layout> L;  // per entry
-  uint64_t npkts = 0, nchunks = 0, wire_bytes = 0, entries = 0;
-};
-
-// Fills the out fields of every entry and the totals.
+// Fills the out fields of every entry and the totals.  The chunk total is
+// judged first, in closed form; the packet total once every entry's out
+// fields are set.
 int layout_batch(hdfs_wire_batch_write *w, size_t n, int proto, int ctype, Batch &B) {
-  if (n > HDFS_WIRE_BATCH_MAX_WRITES)
-    return fail(HDFS_CRC32C_EINVAL, "%zu writes, at most %d in one call", n, HDFS_WIRE_BATCH_MAX_WRITES);
-  if (n && !w) return fail(HDFS_CRC32C_EINVAL, "null writes");
-  for (size_t k = 0; k < n; k++) w[k].wire_len = w[k].npkts = w[k].first_pkt = 0;
-  // the arguments and the chunk total first, in closed form: a batch past the
-  // limit is refused before any write's packets are walked
-  uint64_t chunks = 0;
-  for (size_t k = 0; k < n; k++) {
-    if (!args_ok(proto, ctype, w[k].offset_in_block, w[k].len)) return entry_fail(HDFS_CRC32C_EINVAL, k);
-    const uint64_t mis = uint64_t(w[k].offset_in_block) % kChunk, to_grid = mis ? kChunk - mis : 0u;
-    const uint64_t n0 = std::min(w[k].len, to_grid);
-    chunks += (n0 ? 1u : 0u) + (w[k].len - n0 + kChunk - 1) / kChunk;  // <= 2^31 + 1 each, 65 536 of them
-  }
-  if (chunks > kMaxChunks)
-    return fail(HDFS_CRC32C_EINVAL, "%llu chunks in the batch, at most %llu", (unsigned long long)chunks,
+  Counts c;
+  int rc = count_batch(w, n, HDFS_WIRE_BATCH_MAX_WRITES, proto, ctype, c);
+  if (rc) return rc;
+  if (c.chunks > kMaxChunks)
+    return fail(HDFS_CRC32C_EINVAL, "%llu chunks in the batch, at most %llu", (unsigned long long)c.chunks,
                 (unsigned long long)kMaxChunks);
-  B.L.resize(n);
-  for (size_t k = 0; k < n; k++) {
-    Layout &L = B.L[k];
-    const int rc = build_layout(w[k].len, w[k].offset_in_block, w[k].seqno, proto, ctype, w[k].finish != 0, L);
-    if (rc) return entry_fail(rc, k);
-    w[k].wire_len = L.wire_len;
-    w[k].npkts = L.plan.size();
-    w[k].first_pkt = B.npkts;
-    B.npkts += L.plan.size();
-    B.nchunks += L.nchunks;
-    B.wire_bytes += L.wire_len;
-    B.entries += L.plan.empty() ? 0u : 1u;
-  }
-  // every entry's out fields are set before the totals are judged
+  if ((rc = layout_entries(w, n, proto, ctype, B))) return rc;
   if (B.npkts > kMaxPackets)
     return fail(HDFS_CRC32C_EINVAL, "%llu packets in the batch, at most %llu", (unsigned long long)B.npkts,
                 (unsigned long long)kMaxPackets);
-  if (B.nchunks != chunks) return fail(HDFS_CRC32C_EINVAL, "internal: the batch's chunk counts do not add up");
+  if (B.nchunks != c.chunks) return fail(HDFS_CRC32C_EINVAL, "internal: the batch's chunk counts do not add up");
   return HDFS_CRC32C_OK;
-}
-
-void fill_batch_records(const hdfs_wire_batch_write *w, const Batch &B, hdfs_crc32c_out_packet *pkts) {
-  for (size_t k = 0; k < B.L.size(); k++) fill_records(B.L[k], pkts + w[k].first_pkt);
 }
 
 // ---- device scratch -----------------------------------------------------------
@@ -87,66 +55,18 @@ void fill_batch_records(const hdfs_wire_batch_write *w, const Batch &B, hdfs_crc
 // and tables are never overwritten under its kernel.
 std::mutex g_mu;
 struct Scratch : DeviceScratch {
-  DeviceBuffer crc, tab;
-  PinnedBuffer<> pin;                     // the tables' staging area: tab's twin, grown with it
-  hipEvent_t ev[2] = {nullptr, nullptr};  // of the timing call, created when it first runs
+  DeviceBuffer crc;
+  TablePair tab;
 
   int reserve(int to, size_t crc_bytes, size_t tab_bytes) {
     int rc = bind(to, "stream", [this] {
       crc.release();
       tab.release();
-      pin.release();
-      for (hipEvent_t &e : ev) {
-        if (e) (void)hipEventDestroy(e);
-        e = nullptr;
-      }
     });
     if (rc || (rc = crc.reserve(crc_bytes, kScratchFloor))) return rc;
-    if (tab_bytes <= tab.cap) return HDFS_CRC32C_OK;
-    tab.release();  // both go before either comes back
-    pin.release();
-    if (tab.reserve(tab_bytes, kTableFloor) || pin.reserve(tab_bytes, kTableFloor)) {
-      tab.release();
-      return fail(HDFS_CRC32C_ENOMEM, "allocation of %zu table bytes failed", std::max(tab_bytes, kTableFloor));
-    }
-    return HDFS_CRC32C_OK;
-  }
-  int timing_events() {
-    if (!ev[0] && (hipEventCreate(&ev[0]) != hipSuccess || hipEventCreate(&ev[1]) != hipSuccess))
-      return fail(HDFS_CRC32C_EHIP, "events: %s", hipGetErrorString(hipGetLastError()));
-    return HDFS_CRC32C_OK;
+    return tab.reserve(tab_bytes, kTableFloor);
   }
 } g_s;
-
-// ---- where the buffers live -------------------------------------------------------
-// No wire range overlaps another wire range or a data range: the intervals
-// sorted by their first byte, then one pass that remembers the furthest end
-// among the wire ranges and among the data ranges seen so far.
-struct Span {
-  uintptr_t lo, hi;  // [lo, hi), not empty
-  uint32_t k;        // entry
-  uint32_t wire;     // 1: a wire range
-};
-
-int check_overlaps(std::vector<Span> &v) {
-  std::sort(v.begin(), v.end(), [](const Span &a, const Span &b) {
-    return a.lo != b.lo ? a.lo < b.lo : (a.wire != b.wire ? a.wire > b.wire : a.k < b.k);
-  });
-  const Span *far_w = nullptr, *far_d = nullptr;
-  for (const Span &s : v) {
-    // every span ahead of s starts at or below s.lo: it overlaps s iff it ends behind s.lo
-    if (far_w && far_w->hi > s.lo) {
-      const uint32_t a = std::max(far_w->k, s.k), b = std::min(far_w->k, s.k);
-      return s.wire ? fail(HDFS_CRC32C_EINVAL, "entry %u: wire overlaps the wire of entry %u", a, b)
-                    : fail(HDFS_CRC32C_EINVAL, "entry %u: wire overlaps the data of entry %u", far_w->k, s.k);
-    }
-    if (s.wire && far_d && far_d->hi > s.lo)
-      return fail(HDFS_CRC32C_EINVAL, "entry %u: wire overlaps the data of entry %u", s.k, far_d->k);
-    const Span *&far = s.wire ? far_w : far_d;
-    if (!far || s.hi > far->hi) far = &s;
-  }
-  return HDFS_CRC32C_OK;
-}
 
 // ---- the call -------------------------------------------------------------------------
 // iters == 0: the call of hdfs_wire_batch_compose.  iters > 0: the same, then
@@ -160,50 +80,17 @@ int compose(hdfs_wire_batch_write *w, size_t n, int proto, int ctype, hdfs_crc32
   if (npkts) *npkts = size_t(B.npkts);
   if (rc) return rc;
   const bool fits = pkts && max_pkts >= B.npkts;
-  size_t with_wire = 0;
-  for (size_t k = 0; k < n; k++) with_wire += w[k].wire ? 1u : 0u;
+  const size_t with_wire = count_wires(w, n);
   if (!with_wire) {  // size query; the records are closed-form, so they are filled when they fit
     if (fits) fill_batch_records(w, B, pkts);
     return HDFS_CRC32C_OK;
   }
-  if (with_wire != n) {
-    const bool first = w[0].wire != nullptr;
-    size_t k = 1;
-    while ((w[k].wire != nullptr) == first) k++;
-    return fail(HDFS_CRC32C_EINVAL, "entry %zu: wire is %s, entry 0's is not (every wire NULL is a size query)", k,
-                first ? "NULL" : "set");
-  }
-  for (size_t k = 0; k < n; k++) {
-    if (w[k].len && !w[k].data)
-      return fail(HDFS_CRC32C_EINVAL, "entry %zu: null data with %llu bytes", k, (unsigned long long)w[k].len);
-    if (w[k].wire_cap < w[k].wire_len)
-      return fail(HDFS_CRC32C_EINVAL, "entry %zu: %llu stream bytes, room for %llu", k,
-                  (unsigned long long)w[k].wire_len, (unsigned long long)w[k].wire_cap);
-    if (pkts && w[k].first_pkt + w[k].npkts > max_pkts)
-      return fail(HDFS_CRC32C_EINVAL, "entry %zu: its records end at %llu of %llu, room for %zu", k,
-                  (unsigned long long)(w[k].first_pkt + w[k].npkts), (unsigned long long)B.npkts, max_pkts);
-  }
+  if ((rc = check_entries(w, n, with_wire, B, pkts, max_pkts))) return rc;
   if (!B.npkts) return HDFS_CRC32C_OK;  // nothing but empty writes without finish: no packet
   int dev = -1;
   if ((rc = engine_device(&dev))) return rc;
   DeviceGuard g(dev);
-  {
-    Allocations al;
-    std::vector<Span> spans;
-    spans.reserve(2 * n);
-    for (size_t k = 0; k < n; k++) {
-      const uintptr_t a = reinterpret_cast<uintptr_t>(w[k].data), b = reinterpret_cast<uintptr_t>(w[k].wire);
-      if (w[k].len) {
-        if ((rc = al.check(w[k].data, w[k].len, dev, "data"))) return entry_fail(rc, k);
-        spans.push_back(Span{a, a + uintptr_t(w[k].len), uint32_t(k), 0u});
-      }
-      if (w[k].wire_len) {
-        if ((rc = al.check(w[k].wire, w[k].wire_len, dev, "wire"))) return entry_fail(rc, k);
-        spans.push_back(Span{b, b + uintptr_t(w[k].wire_len), uint32_t(k), 1u});
-      }
-    }
-    if ((rc = check_overlaps(spans))) return rc;
-  }
+  if ((rc = check_batch_places(w, n, dev))) return rc;
   const bool crcs = ctype != HDFS_CRC32C_CSUM_NULL;
   const uint32_t nw = uint32_t(B.entries), total = uint32_t(B.npkts);
   const size_t tab_bytes = batch_table_bytes(nw);
@@ -215,7 +102,7 @@ int compose(hdfs_wire_batch_write *w, size_t n, int proto, int ctype, hdfs_crc32
   // prefix of their packet counts; the CRCs: every write's chunk grid as
   // segments of one compute plan, write k's CRCs behind those of the writes
   // ahead of it
-  Write *tab = g_s.pin.as<Write>();
+  Write *tab = g_s.tab.pin.as<Write>();
   uint32_t *pk0 = reinterpret_cast<uint32_t *>(tab + nw);
   std::vector<hdfs_crc32c_segment> segs;
   if (crcs) segs.reserve(2 * size_t(nw));
@@ -243,10 +130,10 @@ int compose(hdfs_wire_batch_write *w, size_t n, int proto, int ctype, hdfs_crc32
   if (!segs.empty() && (rc = hdfs_crc32c_plan_create(&cplan, HDFS_CRC32C_MODE_COMPUTE, segs.data(), segs.size())))
     return engine_fail(rc, "compute plan");
   hipStream_t st = stream ? static_cast<hipStream_t>(stream) : g_s.st;
-  const hipError_t up = hipMemcpyAsync(g_s.tab.p, g_s.pin.p, tab_bytes, hipMemcpyHostToDevice, st);
+  const hipError_t up = hipMemcpyAsync(g_s.tab.dev.p, g_s.tab.pin.p, tab_bytes, hipMemcpyHostToDevice, st);
   // the CRC array and the tables are out of use when this returns, so before the lock goes
   rc = timed_frame_run(st, up, cplan, g_s.ev, iters, ms_per_iter, "wire batch",
-                       [&] { return launch_frame_batch(g_s.tab.p, nw, total, st); });
+                       [&] { return launch_frame_batch(g_s.tab.dev.p, nw, total, st); });
   if (rc) return rc;
   if (fits) fill_batch_records(w, B, pkts);
   return HDFS_CRC32C_OK;
@@ -265,15 +152,7 @@ const char *hdfs_wire_batch_last_error(void) { return last_error(); }
 
 int hdfs_wire_batch_layout(hdfs_wire_batch_write *w, size_t nwrites, int proto, int ctype,
                            hdfs_wire_batch_totals *out) {
-  if (!out) return fail(HDFS_CRC32C_EINVAL, "null out");
-  std::memset(out, 0, sizeof(*out));
-  Batch B;
-  const int rc = layout_batch(w, nwrites, proto, ctype, B);
-  out->npkts = B.npkts;
-  out->nchunks = B.nchunks;
-  out->wire_bytes = B.wire_bytes;
-  out->table_entries = B.entries;
-  return rc;
+  return layout_totals(out, [&](Batch &B) { return layout_batch(w, nwrites, proto, ctype, B); });
 }
 
 int hdfs_wire_batch_compose(hdfs_wire_batch_write *w, size_t nwrites, int proto, int ctype,
@@ -285,9 +164,8 @@ int hdfs_wire_batch_frame_time(hdfs_wire_batch_write *w, size_t nwrites, int pro
                                double *ms_per_iter) {
   if (iters < 1 || !ms_per_iter) return fail(HDFS_CRC32C_EINVAL, "iters >= 1 and ms_per_iter are needed");
   *ms_per_iter = 0;
-  size_t with_wire = 0;
-  for (size_t k = 0; w && k < nwrites && k < HDFS_WIRE_BATCH_MAX_WRITES; k++) with_wire += w[k].wire ? 1u : 0u;
-  if (!with_wire) return fail(HDFS_CRC32C_EINVAL, "stream buffers are needed");
+  const size_t listed = std::min(nwrites, size_t(HDFS_WIRE_BATCH_MAX_WRITES));  // a longer list is compose's to refuse
+  if (!w || !count_wires(w, listed)) return fail(HDFS_CRC32C_EINVAL, "stream buffers are needed");
   return compose(w, nwrites, proto, ctype, nullptr, 0, nullptr, nullptr, iters, ms_per_iter);
 }
 

@@ -5,14 +5,14 @@
 // hdfs_crc32c_bound_device, its public API) and both share one HIP runtime.
 // Unlike libhadoofus_wire.so it asks that library for no CRC: its own kernel
 // (frame_fused_kernel) computes the chunk CRCs from the bytes it copies, from
-// tables built here out of crc32c_tables.h.
+// tables (wire_fused_host.h) built out of crc32c_tables.h.
 #include <hip/hip_runtime.h>
 
 #include <mutex>
-#include <vector>
 
 #include "crc32c_outpkt.h"
 #include "hadoofus_wire_fused.h"
+#include "wire_fused_host.h"
 #include "wire_fused_internal.h"
 #include "wire_fused_tables.h"
 #include "wire_layout.h"
@@ -23,44 +23,17 @@ namespace {
 using namespace hdfs_wire;  // the layout of a write, its records, the timed run: wire_layout.h's
 
 // ---- device state -------------------------------------------------------------
-// The compact tables of both polynomials (CRC32C first) on the engine's
-// device, uploaded when the library is first used there and kept; the
-// workgroups of one launch, one per CU.  Calls hold g_mu from the launch to
-// the final synchronise.
+// The CRC tables on the engine's device and the workgroups of one launch
+// (wire_fused_host.h), set up when the library is first used there and kept.
+// Calls hold g_mu from the launch to the final synchronise.
 std::mutex g_mu;
+using Fused = DeviceState<prepare_frame_fused, kMaxGroups>;
 struct Scratch : DeviceScratch {
-  DeviceBuffer tab;
-  bool ready = false;
-  uint32_t groups = 0;
-  hipEvent_t ev[2] = {nullptr, nullptr};  // of the timing call, created when it first runs
+  Fused fused;
 
   int reserve(int to) {
-    int rc = bind(to, "stream", [this] {
-      tab.release();
-      ready = false;
-      for (hipEvent_t &e : ev) {
-        if (e) (void)hipEventDestroy(e);
-        e = nullptr;
-      }
-    });
-    if (rc || ready) return rc;
-    std::vector<uint32_t> host(2 * crc::kCompactWords);
-    crc::make_compact(hdfs_crc32c::kPoly, host.data());
-    crc::make_compact(hdfs_crc32c::kPolyZlib, host.data() + crc::kCompactWords);
-    if ((rc = tab.reserve(host.size() * sizeof(uint32_t), 0))) return rc;
-    int cus = 0;
-    hipError_t e = hipMemcpy(tab.p, host.data(), host.size() * sizeof(uint32_t), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, to);
-    if (e == hipSuccess) e = prepare_frame_fused();
-    if (e != hipSuccess) return fail(HDFS_CRC32C_EHIP, "tables: %s", hipGetErrorString(e));
-    groups = cus < 1 ? 1u : (uint32_t(cus) > kMaxGroups ? kMaxGroups : uint32_t(cus));
-    ready = true;
-    return HDFS_CRC32C_OK;
-  }
-  int timing_events() {
-    if (!ev[0] && (hipEventCreate(&ev[0]) != hipSuccess || hipEventCreate(&ev[1]) != hipSuccess))
-      return fail(HDFS_CRC32C_EHIP, "events: %s", hipGetErrorString(hipGetLastError()));
-    return HDFS_CRC32C_OK;
+    const int rc = bind(to, "stream", [this] { fused.release(); });
+    return rc ? rc : fused.setup(to);
   }
 } g_s;
 
@@ -87,8 +60,7 @@ int compose(const void *data, uint64_t len, int64_t off, int64_t seq, int proto,
   if (len && !data) return fail(HDFS_CRC32C_EINVAL, "null data with %llu bytes", (unsigned long long)len);
   if ((pkts && !fits) || wire_cap < L.wire_len)
     return fail(HDFS_CRC32C_EINVAL, "need %zu packets / %llu stream bytes", L.plan.size(), (unsigned long long)L.wire_len);
-  const unsigned want = flags >> 8;
-  if ((flags & 0xFFu) || want > kMaxGroups) return fail(HDFS_CRC32C_EINVAL, "1 to %u workgroups", kMaxGroups);
+  if ((rc = Fused::flags_ok(flags))) return rc;
   if (!L.wire_len) return HDFS_CRC32C_OK;  // an empty write without finish: no packet
   int dev = -1;
   if ((rc = engine_device(&dev))) return rc;
@@ -103,9 +75,8 @@ int compose(const void *data, uint64_t len, int64_t off, int64_t seq, int proto,
   w.data = static_cast<const uint8_t *>(data);
   w.crc = nullptr;
   w.wire = static_cast<uint8_t *>(wire);
-  const uint32_t *tab = g_s.tab.as<uint32_t>() + (ctype == HDFS_CRC32C_CSUM_CRC32 ? crc::kCompactWords : 0u);
-  // the product's grid: a workgroup per CU, and none without a packet
-  const uint32_t groups = want ? want : (w.npk < g_s.groups ? w.npk : g_s.groups);
+  const uint32_t *tab = g_s.fused.tables(ctype);
+  const uint32_t groups = g_s.fused.grid(flags, w.npk);
   hipStream_t st = stream ? static_cast<hipStream_t>(stream) : g_s.st;
   rc = timed_frame_run(st, hipSuccess, nullptr, g_s.ev, iters, ms_per_iter, "fused wire stream",
                        [&] { return launch_frame_fused(w, tab, groups, st); });

@@ -1,9 +1,11 @@
-// Host side shared by libhadoofus_wire.so (wire.cpp) and
-// libhadoofus_wire_batch.so (wire_batch.cpp) only: the layout of one write's
-// stream, its packet records, the compute-plan segments of its chunk grid and
-// the timed frame run.  One definition, included by both.  What every
-// companion library shares (last error, DeviceGuard, device_range, ...) is
-// companion_support.h's.
+// Host side shared by the six wire-stream libraries (wire.cpp, wire_batch.cpp,
+// wirev.cpp, wire_fused.cpp, wire_fused_batch.cpp, wirev_fused.cpp): the
+// layout of one write's stream, its packet records, the compute-plan segments
+// of its chunk grid (the two-pass libraries') and the timed frame run.  One
+// definition, included by all.  What every companion library shares (last
+// error, DeviceGuard, device_range, ...) is companion_support.h's; what only
+// the batch libraries share is wire_batch_layout.h's, what only the fused
+// ones share wire_fused_host.h's.
 #ifndef HADOOFUS_WIRE_LAYOUT_H
 #define HADOOFUS_WIRE_LAYOUT_H
 

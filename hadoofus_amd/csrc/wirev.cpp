@@ -33,7 +33,6 @@ using hdfs_wire::Write;
 // library's, as measured there: plain stores,
 // hdfs_wire::kSlices workgroups per packet.
 constexpr bool kSc1Stores = false;
-constexpr size_t kTableFloor = size_t(16) << 10;
 
 // ---- the fragments ------------------------------------------------------------------
 struct Frags {
@@ -85,9 +84,8 @@ uint32_t max_frags_per_packet(const Frags &F, const std::vector<hdfs_crc32c::out
 std::mutex g_mu;
 struct Scratch : DeviceScratch {
   uint32_t *slice = nullptr;  // u32[2][kSliceWords]: CRC32C, CRC32 (gather_chunks_kernel's)
-  DeviceBuffer crc, gtab, ftab;
-  PinnedBuffer<> pin;                     // the fragment table's staging area: ftab's twin, grown with it
-  hipEvent_t ev[2] = {nullptr, nullptr};  // of the timing call, created when it first runs
+  DeviceBuffer crc, gtab;
+  TablePair ftab;  // the fragment table
 
   int reserve(int to, size_t crc_bytes, size_t gtab_bytes, size_t ftab_bytes) {
     auto release_own = [this] {
@@ -96,11 +94,6 @@ struct Scratch : DeviceScratch {
       crc.release();
       gtab.release();
       ftab.release();
-      pin.release();
-      for (hipEvent_t &e : ev) {
-        if (e) (void)hipEventDestroy(e);
-        e = nullptr;
-      }
     };
     int rc = bind(to, "stream and tables", release_own);
     if (rc) return rc;
@@ -112,41 +105,9 @@ struct Scratch : DeviceScratch {
       }
     }
     if ((rc = crc.reserve(crc_bytes, kScratchFloor)) || (rc = gtab.reserve(gtab_bytes, kScratchFloor))) return rc;
-    if (ftab_bytes <= ftab.cap) return HDFS_CRC32C_OK;
-    ftab.release();  // both go before either comes back
-    pin.release();
-    if (ftab.reserve(ftab_bytes, kTableFloor) || pin.reserve(ftab_bytes, kTableFloor)) {
-      ftab.release();
-      return fail(HDFS_CRC32C_ENOMEM, "allocation of %zu table bytes failed", std::max(ftab_bytes, kTableFloor));
-    }
-    return HDFS_CRC32C_OK;
-  }
-  int timing_events() {
-    if (!ev[0] && (hipEventCreate(&ev[0]) != hipSuccess || hipEventCreate(&ev[1]) != hipSuccess))
-      return fail(HDFS_CRC32C_EHIP, "events: %s", hipGetErrorString(hipGetLastError()));
-    return HDFS_CRC32C_OK;
+    return ftab.reserve(ftab_bytes, kTableFloor);
   }
 } g_s;
-
-// ---- where the buffers live -------------------------------------------------------
-// Every non-empty fragment inside one allocation of device `dev`, the stream
-// inside one, and the stream clear of every fragment.
-int check_places(const hdfs_crc32c_iovec *iov, int n, const void *wire, uint64_t wire_len, int dev) {
-  int rc;
-  Allocations al;
-  const uintptr_t w0 = reinterpret_cast<uintptr_t>(wire), w1 = w0 + uintptr_t(wire_len);
-  for (int i = 0; i < n; i++) {
-    if (!iov[i].len) continue;
-    if ((rc = al.check(iov[i].base, iov[i].len, dev, "data"))) return prefix_fail(rc, "fragment %d", i);
-  }
-  if ((rc = al.check(wire, wire_len, dev, "wire"))) return rc;
-  for (int i = 0; i < n; i++) {
-    const uintptr_t a = reinterpret_cast<uintptr_t>(iov[i].base);
-    if (iov[i].len && a < w1 && w0 < a + uintptr_t(iov[i].len))
-      return fail(HDFS_CRC32C_EINVAL, "fragment %d and wire overlap", i);
-  }
-  return HDFS_CRC32C_OK;
-}
 
 // ---- the call -------------------------------------------------------------------------
 // iters == 0: the call of hdfs_wirev_compose_packets.  iters > 0: the same,
@@ -206,7 +167,7 @@ int compose(const hdfs_crc32c_iovec *iov, int iovcnt, int64_t off, int64_t seq, 
     return rc;
   // the fragment table, in pinned memory: the non-empty fragments and where
   // each starts in the write, then the sentinel
-  Frag *tab = g_s.pin.as<Frag>();
+  Frag *tab = g_s.ftab.pin.as<Frag>();
   uint64_t at = 0;
   uint32_t e = 0;
   for (int i = 0; i < iovcnt; i++) {
@@ -222,13 +183,13 @@ int compose(const hdfs_crc32c_iovec *iov, int iovcnt, int64_t off, int64_t seq, 
   hdfs_crc32c_plan *cplan = nullptr;
   if (crcs && (rc = hdfs_writev::gather_plan(iov, G, ctype, g_s.crc.as<uint32_t>(), &cplan))) return rc;
   hipStream_t st = stream ? static_cast<hipStream_t>(stream) : g_s.st;
-  hipError_t he = hipMemcpyAsync(g_s.ftab.p, g_s.pin.p, ftab_bytes, hipMemcpyHostToDevice, st);
+  hipError_t he = hipMemcpyAsync(g_s.ftab.dev.p, g_s.ftab.pin.p, ftab_bytes, hipMemcpyHostToDevice, st);
   if (he == hipSuccess && crcs)
     rc = hdfs_writev::enqueue_gather(G, cplan, ctype, g_s.gtab.p, g_s.slice, g_s.crc.as<uint32_t>(), st, &he);
   // the CRC array and the tables are out of use when either returns, so before the lock goes
   if (rc || he != hipSuccess) return sync_and_report(st, he, rc, cplan, "gather wire stream");
   rc = hdfs_wire::timed_frame_run(st, hipSuccess, nullptr, g_s.ev, iters, ms_per_iter, "gather wire stream",
-                                  [&] { return launch_frame_gather(w, g_s.ftab.as<Frag>(), nf, sc1, st); });
+                                  [&] { return launch_frame_gather(w, g_s.ftab.dev.as<Frag>(), nf, sc1, st); });
   if (cplan) hdfs_crc32c_plan_destroy(cplan);
   if (rc) return rc;
   if (fits) hdfs_wire::fill_records(L, pkts);

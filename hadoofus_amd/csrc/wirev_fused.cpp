@@ -5,13 +5,12 @@
 // hdfs_crc32c_bound_device, its public API) and both share one HIP runtime.
 // Unlike libhadoofus_wirev.so it asks that library for no CRC and has no
 // gather layout: its own kernel (frame_fused_gather_kernel) computes the chunk
-// CRCs from the bytes it copies out of the fragments, from tables built here
-// out of crc32c_tables.h, and finds the fragments through one table uploaded
+// CRCs from the bytes it copies out of the fragments, from tables
+// (wire_fused_host.h) built out of crc32c_tables.h, and finds the fragments through one table uploaded
 // per call.  The stream's geometry and records are wire_layout.h's.  It links
 // no other companion.
 #include <hip/hip_runtime.h>
 
-#include <algorithm>
 #include <cstring>
 #include <mutex>
 #include <vector>
@@ -19,6 +18,7 @@
 #include "companion_support.h"
 #include "crc32c_outpkt.h"
 #include "hadoofus_wirev_fused.h"
+#include "wire_fused_host.h"
 #include "wire_fused_tables.h"
 #include "wire_layout.h"
 #include "wirev_fused_internal.h"
@@ -28,9 +28,6 @@ namespace hdfs_wirev_fused {
 namespace {
 
 using namespace hdfs_companion;
-namespace crc = hdfs_wire_fused::crc;
-
-constexpr size_t kTableFloor = size_t(16) << 10;
 
 // ---- the fragments ------------------------------------------------------------------
 // Where every non-empty fragment starts in the write, and the write's length
@@ -56,80 +53,27 @@ int sum_fragments(const uint64_t *lens, const hdfs_crc32c_iovec *iov, int n, Fra
 }
 
 // ---- device state -------------------------------------------------------------
-// The compact tables of both polynomials (CRC32C first) on the engine's
-// device, uploaded when the library is first used there and kept; the
-// workgroups of one launch, one per CU; the fragment table with its pinned
-// staging twin, grown on demand, never shrunk, kept between calls.  Calls
+// The CRC tables on the engine's device and the workgroups of one launch
+// (wire_fused_host.h), set up when the library is first used there and kept;
+// the fragment table with its pinned staging twin, grown on demand, never
+// shrunk, kept between calls.  Calls
 // hold g_mu from the table's upload to the final synchronise, so one call's
 // table is never overwritten under its kernel.
 std::mutex g_mu;
+using Fused = hdfs_wire_fused::DeviceState<prepare_frame_fused_gather, kMaxGroups>;
 struct Scratch : DeviceScratch {
-  DeviceBuffer tab, ftab;
-  PinnedBuffer<> pin;  // the fragment table's staging area: ftab's twin, grown with it
-  bool ready = false;
-  uint32_t groups = 0;
-  hipEvent_t ev[2] = {nullptr, nullptr};  // of the timing call, created when it first runs
+  Fused fused;
+  TablePair ftab;  // the fragment table
 
   int reserve(int to, size_t ftab_bytes) {
     int rc = bind(to, "stream and tables", [this] {
-      tab.release();
+      fused.release();
       ftab.release();
-      pin.release();
-      ready = false;
-      for (hipEvent_t &e : ev) {
-        if (e) (void)hipEventDestroy(e);
-        e = nullptr;
-      }
     });
-    if (rc) return rc;
-    if (!ready) {
-      std::vector<uint32_t> host(2 * crc::kCompactWords);
-      crc::make_compact(hdfs_crc32c::kPoly, host.data());
-      crc::make_compact(hdfs_crc32c::kPolyZlib, host.data() + crc::kCompactWords);
-      if ((rc = tab.reserve(host.size() * sizeof(uint32_t), 0))) return rc;
-      int cus = 0;
-      hipError_t e = hipMemcpy(tab.p, host.data(), host.size() * sizeof(uint32_t), hipMemcpyHostToDevice);
-      if (e == hipSuccess) e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, to);
-      if (e == hipSuccess) e = prepare_frame_fused_gather();
-      if (e != hipSuccess) return fail(HDFS_CRC32C_EHIP, "tables: %s", hipGetErrorString(e));
-      groups = cus < 1 ? 1u : (uint32_t(cus) > kMaxGroups ? kMaxGroups : uint32_t(cus));
-      ready = true;
-    }
-    if (ftab_bytes <= ftab.cap) return HDFS_CRC32C_OK;
-    ftab.release();  // both go before either comes back
-    pin.release();
-    if (ftab.reserve(ftab_bytes, kTableFloor) || pin.reserve(ftab_bytes, kTableFloor)) {
-      ftab.release();
-      return fail(HDFS_CRC32C_ENOMEM, "allocation of %zu table bytes failed", std::max(ftab_bytes, kTableFloor));
-    }
-    return HDFS_CRC32C_OK;
-  }
-  int timing_events() {
-    if (!ev[0] && (hipEventCreate(&ev[0]) != hipSuccess || hipEventCreate(&ev[1]) != hipSuccess))
-      return fail(HDFS_CRC32C_EHIP, "events: %s", hipGetErrorString(hipGetLastError()));
-    return HDFS_CRC32C_OK;
+    if (rc || (rc = fused.setup(to))) return rc;
+    return ftab.reserve(ftab_bytes, kTableFloor);
   }
 } g_s;
-
-// ---- where the buffers live -------------------------------------------------------
-// Every non-empty fragment inside one allocation of device `dev`, the stream
-// inside one, and the stream clear of every fragment.
-int check_places(const hdfs_crc32c_iovec *iov, int n, const void *wire, uint64_t wire_len, int dev) {
-  int rc;
-  Allocations al;
-  const uintptr_t w0 = reinterpret_cast<uintptr_t>(wire), w1 = w0 + uintptr_t(wire_len);
-  for (int i = 0; i < n; i++) {
-    if (!iov[i].len) continue;
-    if ((rc = al.check(iov[i].base, iov[i].len, dev, "data"))) return prefix_fail(rc, "fragment %d", i);
-  }
-  if ((rc = al.check(wire, wire_len, dev, "wire"))) return rc;
-  for (int i = 0; i < n; i++) {
-    const uintptr_t a = reinterpret_cast<uintptr_t>(iov[i].base);
-    if (iov[i].len && a < w1 && w0 < a + uintptr_t(iov[i].len))
-      return fail(HDFS_CRC32C_EINVAL, "fragment %d and wire overlap", i);
-  }
-  return HDFS_CRC32C_OK;
-}
 
 // ---- the call -------------------------------------------------------------------------
 // iters == 0: the call of hdfs_wirev_fused_compose_packets.  iters > 0: the
@@ -159,8 +103,7 @@ int compose(const hdfs_crc32c_iovec *iov, int iovcnt, int64_t off, int64_t seq, 
       return fail(HDFS_CRC32C_EINVAL, "fragment %d: null base with %llu bytes", i, (unsigned long long)iov[i].len);
   if ((pkts && !fits) || wire_cap < L.wire_len)
     return fail(HDFS_CRC32C_EINVAL, "need %zu packets / %llu stream bytes", L.plan.size(), (unsigned long long)L.wire_len);
-  const unsigned want = flags >> 8;
-  if ((flags & 0xFFu) || want > kMaxGroups) return fail(HDFS_CRC32C_EINVAL, "1 to %u workgroups", kMaxGroups);
+  if ((rc = Fused::flags_ok(flags))) return rc;
   if (F.nfrags() >= 0xFFFFFFFFull) return fail(HDFS_CRC32C_EINVAL, "more than 2^32 - 2 fragments in one write");
   if (!L.wire_len) return HDFS_CRC32C_OK;  // an empty write without finish: no packet
   int dev = -1;
@@ -173,7 +116,7 @@ int compose(const hdfs_crc32c_iovec *iov, int iovcnt, int64_t off, int64_t seq, 
   if ((rc = g_s.reserve(dev, ftab_bytes)) || (iters && (rc = g_s.timing_events()))) return rc;
   // the fragment table, in pinned memory: the non-empty fragments and where
   // each starts in the write, then the sentinel
-  Frag *ft = g_s.pin.as<Frag>();
+  Frag *ft = g_s.ftab.pin.as<Frag>();
   uint32_t e = 0;
   for (int i = 0; i < iovcnt; i++)
     if (iov[i].len) {
@@ -186,14 +129,13 @@ int compose(const hdfs_crc32c_iovec *iov, int iovcnt, int64_t off, int64_t seq, 
   w.data = nullptr;  // the data are the fragments': the kernel counts in their concatenation
   w.crc = nullptr;
   w.wire = static_cast<uint8_t *>(wire);
-  const uint32_t *tab = g_s.tab.as<uint32_t>() + (ctype == HDFS_CRC32C_CSUM_CRC32 ? crc::kCompactWords : 0u);
-  // the product's grid: a workgroup per CU, and none without a packet
-  const uint32_t groups = want ? want : (w.npk < g_s.groups ? w.npk : g_s.groups);
+  const uint32_t *tab = g_s.fused.tables(ctype);
+  const uint32_t groups = g_s.fused.grid(flags, w.npk);
   hipStream_t st = stream ? static_cast<hipStream_t>(stream) : g_s.st;
-  const hipError_t he = hipMemcpyAsync(g_s.ftab.p, g_s.pin.p, ftab_bytes, hipMemcpyHostToDevice, st);
+  const hipError_t he = hipMemcpyAsync(g_s.ftab.dev.p, g_s.ftab.pin.p, ftab_bytes, hipMemcpyHostToDevice, st);
   // the table is out of use when this returns, so before the lock goes
   rc = hdfs_wire::timed_frame_run(st, he, nullptr, g_s.ev, iters, ms_per_iter, "fused gather wire stream",
-                                  [&] { return launch_frame_fused_gather(w, g_s.ftab.as<Frag>(), nf, tab, groups, st); });
+                                  [&] { return launch_frame_fused_gather(w, g_s.ftab.dev.as<Frag>(), nf, tab, groups, st); });
   if (rc) return rc;
   if (fits) hdfs_wire::fill_records(L, pkts);
   return HDFS_CRC32C_OK;

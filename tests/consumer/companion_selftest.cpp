@@ -1,11 +1,13 @@
 // CPU self-test of the companion libraries' shared host support
-// (hadoofus_amd/csrc/companion_support.h, and grid_segments / timed_frame_run
-// of wire_layout.h) against a fake HIP runtime and a fake engine, both
-// defined here: the program is not linked to the HIP runtime.  The fakes count
-// and log every call, remember the current device and can be told to fail, so
-// the checks cover what the GPU tests cannot: failed allocations and streams,
-// a device change, the exact runtime calls of a warm call.  Prints
-// "N failures".
+// (hadoofus_amd/csrc/companion_support.h, grid_segments / timed_frame_run of
+// wire_layout.h, the fused libraries' device state of wire_fused_host.h and
+// the batch front end of wire_batch_layout.h) against a fake HIP runtime and a
+// fake engine, both defined here: the program is not linked to the HIP
+// runtime.  The fakes count and log every call, remember the current device
+// and can be told to fail, so the checks cover what the GPU tests cannot:
+// failed allocations, streams and events, a device change, the exact runtime
+// calls of a warm call, and the code that a call reaches only once a device
+// has been found (where the buffers of a batch lie).  Prints "N failures".
 #include <algorithm>
 #include <cstdint>
 #include <cstdio>
@@ -17,6 +19,8 @@
 #include <vector>
 
 #include "companion_support.h"
+#include "wire_batch_layout.h"
+#include "wire_fused_host.h"
 #include "wire_layout.h"
 
 using namespace hdfs_companion;
@@ -48,6 +52,10 @@ struct Fake {
   int calls = 0;                        // all runtime calls
   hipError_t sticky = hipSuccess;
   int fail_malloc = 0, fail_host_malloc = 0, fail_stream = 0, fail_sync = 0, fail_range = 0, fail_launch = 0;
+  int fail_event = 0;  // n > 0: the n-th hipEventCreate from now fails
+  int events = 0;      // live events
+  int cus = 256;       // hipDeviceGetAttribute's answer
+  size_t copied = 0;   // bytes of the last hipMemcpy
   bool any_range = false;  // an address inside no block is reported as part of the lowest block
   int wrong_device_frees = 0, streams = 0;
   // the fake engine
@@ -71,6 +79,9 @@ struct Fake {
 } F;
 
 struct FakeStream {
+  int device;
+};
+struct FakeEvent {
   int device;
 };
 
@@ -179,6 +190,38 @@ hipError_t hipGetLastError(void) {
 }
 const char *hipGetErrorString(hipError_t e) {
   return e == hipErrorOutOfMemory ? "fake: out of memory" : e == hipErrorLaunchFailure ? "fake: launch failure" : "fake: error";
+}
+hipError_t hipEventCreate(hipEvent_t *e) {
+  F.called("hipEventCreate");
+  if (F.fail_event && !--F.fail_event) {
+    *e = reinterpret_cast<hipEvent_t>(uintptr_t(0xBAD));  // a careless caller would destroy this
+    return F.failed(hipErrorOutOfMemory);
+  }
+  F.events++;
+  *e = reinterpret_cast<hipEvent_t>(new FakeEvent{F.cur});
+  return hipSuccess;
+}
+hipError_t hipEventDestroy(hipEvent_t e) {
+  F.called("hipEventDestroy");
+  FakeEvent *fe = reinterpret_cast<FakeEvent *>(e);
+  if (fe->device != F.cur) F.wrong_device_frees++;
+  delete fe;
+  F.events--;
+  return hipSuccess;
+}
+hipError_t hipMemcpy(void *dst, const void *src, size_t n, hipMemcpyKind) {
+  F.called("hipMemcpy");
+  uintptr_t base = 0;
+  const Block *b = F.find(reinterpret_cast<uintptr_t>(dst), &base);
+  if (!b || !b->owned || n > b->size - (reinterpret_cast<uintptr_t>(dst) - base)) return F.failed(hipErrorInvalidValue);
+  std::memcpy(dst, src, n);
+  F.copied = n;
+  return hipSuccess;
+}
+hipError_t hipDeviceGetAttribute(int *v, hipDeviceAttribute_t, int) {
+  F.called("hipDeviceGetAttribute");
+  *v = F.cus;
+  return hipSuccess;
 }
 hipError_t hipEventRecord(hipEvent_t, hipStream_t) {
   F.called("hipEventRecord");
@@ -398,6 +441,182 @@ void test_scratch() {
   CHECK(F.cur == 0);
 }
 
+// ---- the two events of a timing call -----------------------------------------------------------
+void test_timing_events() {
+  TestScratch s;
+  F.cur = 0;
+  CHECK(s.reserve(0, 100) == 0 && !s.ev[0] && !s.ev[1]);
+  size_t at = F.log.size();
+  CHECK(s.timing_events() == 0 && s.ev[0] && s.ev[1] && F.events == 2);
+  CHECK(names_since(at) == "hipEventCreate hipEventCreate");  // created on first use
+  at = F.log.size();
+  CHECK(s.timing_events() == 0 && s.reserve(0, 100) == 0 && F.log.size() == at);  // a warm call: no runtime call
+  // a device change: destroyed once, behind the library's buffers and ahead of the stream, the old device current
+  F.cur = 2;
+  at = F.log.size();
+  CHECK(s.reserve(2, 100) == 0 && F.events == 0 && !s.ev[0] && !s.ev[1] && F.wrong_device_frees == 0);
+  std::string got;
+  for (size_t i = at; i < F.log.size(); i++) got += F.log[i] + " ";
+  CHECK(got == "hipGetDevice@2 hipSetDevice@0 hipStreamSynchronize@0 hipFree@0 hipFree@0 hipEventDestroy@0 "
+               "hipEventDestroy@0 hipStreamDestroy@0 hipSetDevice@2 hipStreamCreate@2 hipMalloc@2 hipMalloc@2 ");
+  // a failed create: EHIP, the text, the runtime's error cleared, nothing kept; the next call retries
+  F.fail_event = 1;
+  at = F.log.size();
+  CHECK(s.timing_events() == HDFS_CRC32C_EHIP && err_is("events: fake: out of memory") && F.sticky == hipSuccess);
+  CHECK(!s.ev[0] && !s.ev[1] && F.events == 0 && names_since(at) == "hipEventCreate hipGetLastError");
+  // ... and of the second event: the first does not pass for the pair
+  F.fail_event = 2;
+  at = F.log.size();
+  CHECK(s.timing_events() == HDFS_CRC32C_EHIP && err_is("events: fake: out of memory") && F.sticky == hipSuccess);
+  CHECK(!s.ev[0] && !s.ev[1] && F.events == 0);
+  CHECK(names_since(at) == "hipEventCreate hipEventCreate hipEventDestroy hipGetLastError");
+  at = F.log.size();
+  CHECK(s.timing_events() == 0 && s.ev[0] && s.ev[1] && F.events == 2);
+  CHECK(names_since(at) == "hipEventCreate hipEventCreate");
+  at = F.log.size();
+  s.unbind([&] {
+    s.a.release();
+    s.b.release();
+  });
+  CHECK(names_since(at) == "hipStreamSynchronize hipFree hipFree hipEventDestroy hipEventDestroy hipStreamDestroy");
+  CHECK(F.events == 0 && F.streams == 0 && F.wrong_device_frees == 0);
+  F.cur = 0;
+}
+
+// ---- a device table and its pinned twin --------------------------------------------------------
+void test_table_pair() {
+  const size_t live = F.blocks.size();
+  auto empty = [](const TablePair &t) { return !t.dev.p && !t.dev.cap && !t.pin.p && !t.pin.cap; };
+  CHECK(kTableFloor == 16384 && kScratchFloor == 65536);
+  TablePair t;
+  size_t at = F.log.size();
+  CHECK(t.reserve(0, kTableFloor) == 0 && empty(t) && F.log.size() == at);  // nothing asked, nothing done
+  CHECK(t.reserve(1, kTableFloor) == 0 && t.dev.p && t.pin.p && t.dev.cap == 16384 && t.pin.cap == 16384);
+  CHECK(names_since(at) == "hipMalloc hipHostMalloc");  // the floor
+  const void *d0 = t.dev.p, *p0 = t.pin.p;
+  at = F.log.size();
+  CHECK(t.reserve(16384, kTableFloor) == 0 && t.reserve(5, kTableFloor) == 0 && t.reserve(0, kTableFloor) == 0);
+  CHECK(F.log.size() == at && t.dev.p == d0 && t.pin.p == p0);  // within capacity: no runtime call
+  CHECK(t.reserve(16385, kTableFloor) == 0 && t.dev.cap == 16385 && t.pin.cap == 16385);
+  CHECK(names_since(at) == "hipFree hipHostFree hipMalloc hipHostMalloc");  // both go before either comes back
+  // the device side fails: both {null, 0}, ENOMEM, the text, the runtime's error cleared
+  F.fail_malloc = 1;
+  at = F.log.size();
+  CHECK(t.reserve(1 << 20, kTableFloor) == HDFS_CRC32C_ENOMEM && empty(t) && F.sticky == hipSuccess);
+  CHECK(err_is("allocation of 1048576 table bytes failed"));
+  CHECK(names_since(at) == "hipFree hipHostFree hipMalloc hipGetLastError");
+  at = F.log.size();
+  CHECK(t.reserve(1 << 20, kTableFloor) == 0 && t.dev.cap == (1 << 20) && t.pin.cap == (1 << 20));  // the next call
+  CHECK(names_since(at) == "hipMalloc hipHostMalloc");
+  // the pinned side fails: the device table goes too
+  F.fail_host_malloc = 1;
+  at = F.log.size();
+  CHECK(t.reserve((1 << 20) + 1, kTableFloor) == HDFS_CRC32C_ENOMEM && empty(t) && F.sticky == hipSuccess);
+  CHECK(err_is("allocation of 1048577 table bytes failed"));
+  CHECK(names_since(at) == "hipFree hipHostFree hipMalloc hipHostMalloc hipGetLastError hipFree");
+  // the text counts what was asked of the runtime: max(bytes, floor)
+  F.fail_malloc = 1;
+  CHECK(t.reserve(100, kTableFloor) == HDFS_CRC32C_ENOMEM && empty(t) && err_is("allocation of 16384 table bytes failed"));
+  at = F.log.size();
+  CHECK(t.reserve(100, kTableFloor) == 0 && t.dev.cap == 16384 && names_since(at) == "hipMalloc hipHostMalloc");
+  at = F.log.size();
+  t.release();
+  CHECK(empty(t) && names_since(at) == "hipFree hipHostFree");
+  t.release();
+  CHECK(F.log.size() == at + 2 && F.blocks.size() == live && F.wrong_device_frees == 0);
+}
+
+// ---- the fused libraries' device state ---------------------------------------------------------
+int g_prepares = 0;
+hipError_t g_prepare_rc = hipSuccess;
+hipError_t counted_prepare() {
+  F.called("prepare");
+  g_prepares++;
+  return g_prepare_rc;
+}
+using FusedState = hdfs_wire_fused::DeviceState<counted_prepare, 1024u>;
+
+struct FusedScratch : DeviceScratch {  // as the three libraries build theirs
+  FusedState fused;
+  TablePair tab;
+  int reserve(int to, size_t tab_bytes) {
+    int rc = bind(to, "stream", [this] {
+      fused.release();
+      tab.release();
+    });
+    if (rc || (rc = fused.setup(to))) return rc;
+    return tab.reserve(tab_bytes, kTableFloor);
+  }
+};
+
+void test_fused_state() {
+  namespace crc = hdfs_wire_fused::crc;
+  const size_t live = F.blocks.size(), bytes = 2 * size_t(crc::kCompactWords) * sizeof(uint32_t);
+  std::vector<uint32_t> want(2 * crc::kCompactWords);
+  crc::make_compact(hdfs_crc32c::kPoly, want.data());
+  crc::make_compact(hdfs_crc32c::kPolyZlib, want.data() + crc::kCompactWords);
+  CHECK(std::memcmp(want.data(), want.data() + crc::kCompactWords, bytes / 2) != 0);
+  const int cus[4] = {0, 1, 256, 5000};
+  const uint32_t groups[4] = {1, 1, 256, 1024};
+  for (int i = 0; i < 4; i++) {
+    FusedState s;
+    F.cus = cus[i];
+    F.copied = 0;
+    g_prepares = 0;
+    size_t at = F.log.size();
+    CHECK(s.setup(0) == 0 && s.ready && s.groups == groups[i] && g_prepares == 1);
+    CHECK(names_since(at) == "hipMalloc hipMemcpy hipDeviceGetAttribute prepare");  // one upload, one prepare
+    CHECK(F.copied == bytes && s.crc_tab.cap == bytes && !std::memcmp(s.crc_tab.p, want.data(), bytes));  // CRC32C first
+    at = F.log.size();
+    CHECK(s.setup(0) == 0 && F.log.size() == at && g_prepares == 1);  // a warm call: no runtime call
+    CHECK(s.tables(HDFS_CRC32C_CSUM_CRC32C) == s.crc_tab.as<uint32_t>() && s.tables(HDFS_CRC32C_CSUM_NULL) == s.crc_tab.p);
+    CHECK(s.tables(HDFS_CRC32C_CSUM_CRC32) == s.crc_tab.as<uint32_t>() + crc::kCompactWords);
+    // the grid: a workgroup per CU and none without a packet, unless the flags ask for a number
+    CHECK(s.grid(0u, 1) == 1 && s.grid(0u, groups[i]) == groups[i] && s.grid(0u, 70000) == groups[i]);
+    CHECK(s.grid(7u << 8, 1) == 7 && s.grid(1024u << 8, 3) == 1024);
+    s.release();
+    CHECK(!s.ready && !s.crc_tab.p);
+  }
+  F.cus = 256;
+  CHECK(FusedState::flags_ok(0u) == 0 && FusedState::flags_ok(1u << 8) == 0 && FusedState::flags_ok(1024u << 8) == 0);
+  CHECK(FusedState::flags_ok(1025u << 8) == HDFS_CRC32C_EINVAL && err_is("1 to 1024 workgroups"));
+  CHECK(FusedState::flags_ok((4u << 8) | 1u) == HDFS_CRC32C_EINVAL && err_is("1 to 1024 workgroups"));
+  // in a scratch: a warm call makes no runtime call, a device change uploads and prepares again
+  FusedScratch s;
+  F.cur = 0;
+  g_prepares = 0;
+  size_t at = F.log.size();
+  CHECK(s.reserve(0, 100) == 0 && g_prepares == 1);
+  CHECK(names_since(at) == "hipStreamCreate hipMalloc hipMemcpy hipDeviceGetAttribute prepare hipMalloc hipHostMalloc");
+  at = F.log.size();
+  CHECK(s.reserve(0, 16384) == 0 && s.reserve(0, 0) == 0 && F.log.size() == at && g_prepares == 1);
+  F.cur = 2;
+  at = F.log.size();
+  CHECK(s.reserve(2, 100) == 0 && g_prepares == 2 && s.fused.ready && F.wrong_device_frees == 0);
+  std::string got;
+  for (size_t i = at; i < F.log.size(); i++) got += F.log[i] + " ";
+  CHECK(got == "hipGetDevice@2 hipSetDevice@0 hipStreamSynchronize@0 hipFree@0 hipFree@0 hipHostFree@0 "
+               "hipStreamDestroy@0 hipSetDevice@2 hipStreamCreate@2 hipMalloc@2 hipMemcpy@2 hipDeviceGetAttribute@2 "
+               "prepare@2 hipMalloc@2 hipHostMalloc@2 ");
+  s.unbind([&] {
+    s.fused.release();
+    s.tab.release();
+  });
+  // a failing prepare: EHIP, the text, not ready; the next call uploads and prepares again
+  FusedState f;
+  g_prepare_rc = hipErrorLaunchFailure;
+  CHECK(f.setup(2) == HDFS_CRC32C_EHIP && err_is("tables: fake: launch failure") && !f.ready);
+  g_prepare_rc = hipSuccess;
+  at = F.log.size();
+  CHECK(f.setup(2) == 0 && f.ready && f.groups == 256 && names_since(at) == "hipMemcpy hipDeviceGetAttribute prepare");
+  // a failed table allocation is the buffer's failure
+  f.release();
+  F.fail_malloc = 1;
+  CHECK(f.setup(2) == HDFS_CRC32C_ENOMEM && !f.ready && F.sticky == hipSuccess);
+  F.cur = 0;
+  CHECK(F.blocks.size() == live && F.streams == 0 && F.wrong_device_frees == 0);
+}
+
 // ---- where a pointer lives ----------------------------------------------------------------------
 void test_placement() {
   const uintptr_t A = 0x7000'0000'0000ull, B = 0x7100'0000'0000ull, H = 0x7200'0000'0000ull;
@@ -493,6 +712,316 @@ void test_placement() {
   }
   F.blocks.erase(A);
   F.blocks.erase(B);
+  F.blocks.erase(H);
+}
+
+// ---- a batch: no stream over another stream or over any data -----------------------------------------
+using hdfs_wire::Span;
+
+bool meet(const Span &a, const Span &b) { return a.lo < b.hi && b.lo < a.hi; }
+
+// The verdict by looking at every pair, the sweep's yardstick.
+bool scan_finds_overlap(const std::vector<Span> &v) {
+  for (size_t i = 0; i < v.size(); i++)
+    for (size_t j = i + 1; j < v.size(); j++)
+      if ((v[i].wire || v[j].wire) && meet(v[i], v[j])) return true;
+  return false;
+}
+
+// "entry A: wire overlaps the wire|data of entry B" names spans of v that do overlap.
+bool refusal_names_a_pair(const std::vector<Span> &v) {
+  unsigned a = 0, b = 0;
+  char kind[8] = "";
+  if (std::sscanf(last_error(), "entry %u: wire overlaps the %4s of entry %u", &a, kind, &b) != 3) return false;
+  const bool other_wire = !std::strcmp(kind, "wire");
+  if (!other_wire && std::strcmp(kind, "data")) return false;
+  if (other_wire && a <= b) return false;  // the later entry is the one refused
+  for (const Span &x : v)
+    for (const Span &y : v)
+      if (&x != &y && x.wire && x.k == a && y.wire == (other_wire ? 1u : 0u) && y.k == b && meet(x, y)) return true;
+  return false;
+}
+
+// The sweep sorts its argument; the scan sees the caller's order.
+int g_refused = 0, g_allowed = 0;
+void overlaps_agree(const std::vector<Span> &v) {
+  std::vector<Span> sorted = v;
+  const int rc = hdfs_wire::check_overlaps(sorted);
+  const bool bad = scan_finds_overlap(v);
+  (bad ? g_refused : g_allowed)++;
+  if (rc != (bad ? HDFS_CRC32C_EINVAL : 0) || (bad && !refusal_names_a_pair(v))) {
+    std::printf("  spans:");
+    for (const Span &s : v)
+      std::printf(" %s%u[%llu,%llu)", s.wire ? "w" : "d", s.k, (unsigned long long)s.lo, (unsigned long long)s.hi);
+    std::printf("\n  rc %d, scan %d, text \"%s\"\n", rc, int(bad), rc ? last_error() : "");
+    CHECK(!"check_overlaps agrees with the scan of every pair");
+  }
+}
+
+void test_overlaps() {
+  const uintptr_t B = 0x7400'0000'0000ull;
+  auto one = [&](std::vector<Span> v, const char *text) {
+    for (Span &s : v) s.lo += B, s.hi += B;
+    overlaps_agree(v);
+    const int rc = hdfs_wire::check_overlaps(v);
+    CHECK(text ? rc == HDFS_CRC32C_EINVAL && err_is(text) : rc == 0);
+  };
+  one({}, nullptr);
+  one({{0, 10, 0, 1}}, nullptr);
+  one({{0, 10, 0, 1}, {10, 20, 1, 1}, {20, 30, 1, 0}, {30, 31, 0, 0}}, nullptr);  // touching: hi == lo
+  one({{0, 10, 0, 0}, {5, 15, 1, 0}, {0, 15, 2, 0}, {20, 30, 0, 1}, {30, 40, 1, 1}}, nullptr);  // data over data
+  one({{0, 10, 0, 1}, {9, 20, 1, 1}}, "entry 1: wire overlaps the wire of entry 0");
+  one({{9, 20, 0, 1}, {0, 10, 1, 1}}, "entry 1: wire overlaps the wire of entry 0");
+  one({{0, 10, 3, 1}, {9, 20, 3, 0}}, "entry 3: wire overlaps the data of entry 3");  // a write framed in place
+  one({{0, 10, 0, 0}, {9, 20, 1, 1}}, "entry 1: wire overlaps the data of entry 0");
+  // the same first byte: the wire range is sorted ahead of the data range, and refused either way
+  one({{5, 6, 0, 0}, {5, 9, 1, 1}}, "entry 1: wire overlaps the data of entry 0");
+  one({{5, 9, 0, 0}, {5, 6, 1, 1}}, "entry 1: wire overlaps the data of entry 0");
+  one({{5, 9, 2, 1}, {5, 6, 1, 1}}, "entry 2: wire overlaps the wire of entry 1");
+  // a long wire range swallows later spans that end long before it does
+  one({{0, 100, 0, 1}, {100, 110, 1, 1}, {110, 120, 2, 0}}, nullptr);
+  one({{0, 100, 0, 1}, {200, 210, 1, 1}, {220, 230, 2, 0}, {240, 250, 3, 1}, {90, 91, 4, 0}},
+      "entry 0: wire overlaps the data of entry 4");
+  one({{0, 100, 0, 1}, {200, 210, 1, 0}, {10, 12, 2, 0}, {20, 22, 3, 0}, {50, 51, 4, 1}},
+      "entry 0: wire overlaps the data of entry 2");
+  // ... and a long data range a later wire range, behind shorter data ranges
+  one({{0, 100, 0, 0}, {10, 12, 1, 0}, {20, 22, 2, 0}, {99, 120, 3, 1}}, "entry 3: wire overlaps the data of entry 0");
+  one({{0, 100, 0, 0}, {10, 12, 1, 0}, {20, 22, 2, 0}, {100, 120, 3, 1}}, nullptr);
+  // every batch of up to 4 entries whose one range is [lo, hi) of 6 grid points, wire or data, or empty data
+  // (which the front end leaves out, so the entry has no span)
+  struct Choice {
+    uint32_t lo, hi, wire;  // lo == hi: the empty one
+  };
+  std::vector<Choice> choices{{0, 0, 0}};
+  for (uint32_t lo = 0; lo < 6; lo++)
+    for (uint32_t hi = lo + 1; hi < 6; hi++)
+      for (uint32_t wire = 0; wire < 2; wire++) choices.push_back({lo, hi, wire});
+  CHECK(choices.size() == 31);
+  g_refused = g_allowed = 0;
+  std::vector<Span> v;
+  for (size_t n = 1; n <= 4; n++) {
+    size_t total = 1;
+    for (size_t k = 0; k < n; k++) total *= choices.size();
+    for (size_t code = 0; code < total; code++) {
+      v.clear();
+      size_t c = code;
+      for (uint32_t k = 0; k < n; k++, c /= choices.size()) {
+        const Choice &ch = choices[c % choices.size()];
+        if (ch.lo != ch.hi) v.push_back(Span{B + 16 * ch.lo, B + 16 * ch.hi, k, ch.wire});
+      }
+      overlaps_agree(v);
+    }
+  }
+  CHECK(g_refused > 100000 && g_allowed > 100000);
+  // random batches of up to 32 entries (64 spans), fixed seed: streams laid out one behind another with gaps of
+  // 0 to 3 bytes in a shuffled order, data anywhere in a region of its own, overlapping freely; then, in two
+  // batches of three, one range is moved or stretched by a few bytes
+  uint64_t seed = 0x9E3779B97F4A7C15ull;
+  auto rnd = [&](uint64_t n) {
+    seed ^= seed << 13, seed ^= seed >> 7, seed ^= seed << 17;
+    return (seed >> 11) % n;
+  };
+  g_refused = g_allowed = 0;
+  for (int round = 0; round < 4000; round++) {
+    const uint32_t n = 1 + uint32_t(rnd(32));
+    std::vector<uint32_t> order(n);
+    for (uint32_t k = 0; k < n; k++) order[k] = k;
+    for (uint32_t k = n; k > 1; k--) std::swap(order[k - 1], order[rnd(k)]);
+    v.clear();
+    uintptr_t at = B;
+    for (uint32_t k : order) {
+      const uintptr_t len = 1 + rnd(40);
+      at += rnd(4);
+      v.push_back(Span{at, at + len, k, 1u});
+      at += len;
+    }
+    const uintptr_t D = at + 64;  // the data region
+    for (uint32_t k = 0; k < n; k++)
+      if (rnd(4)) {
+        const uintptr_t lo = D + rnd(40 * n);
+        v.push_back(Span{lo, lo + 1 + rnd(60), k, 0u});
+      }
+    if (round % 3) {
+      Span &s = v[rnd(v.size())];
+      switch (rnd(3)) {
+        case 0: s.hi += 1 + rnd(8); break;
+        case 1: s.lo -= 1 + rnd(8); break;
+        default: {  // somewhere else altogether, streams and data alike
+          const uintptr_t len = s.hi - s.lo;
+          s.lo = B + rnd(D - B + 40 * n);
+          s.hi = s.lo + len;
+        }
+      }
+    }
+    for (size_t k = v.size(); k > 1; k--) std::swap(v[k - 1], v[rnd(k)]);
+    overlaps_agree(v);
+  }
+  CHECK(g_refused > 500 && g_allowed > 500);
+}
+
+// ---- the batch front end, on an entry struct of the public layout ---------------------------------------
+struct TestEntry {
+  const void *data;
+  uint64_t len;
+  int64_t offset_in_block, seqno;
+  int32_t finish, reserved;
+  void *wire;
+  uint64_t wire_cap;
+  uint64_t wire_len, npkts, first_pkt;  // out
+};
+struct TestTotals {
+  uint64_t npkts, nchunks, wire_bytes, table_entries;
+};
+
+// A library's layout_batch with a limit of its own: at most max_packets, judged behind the walk.
+int test_layout_batch(TestEntry *w, size_t n, uint64_t max_packets, hdfs_wire::Batch &B) {
+  hdfs_wire::Counts c;
+  int rc = hdfs_wire::count_batch(w, n, 5, 2, HDFS_CRC32C_CSUM_CRC32C, c);
+  if (rc || (rc = hdfs_wire::layout_entries(w, n, 2, HDFS_CRC32C_CSUM_CRC32C, B))) return rc;
+  CHECK(B.npkts == c.packets && B.nchunks == c.chunks);  // the closed forms count what the walk finds
+  return B.npkts > max_packets ? fail(HDFS_CRC32C_EINVAL, "too many packets") : HDFS_CRC32C_OK;
+}
+
+void test_batch_front_end() {
+  using namespace hdfs_wire;
+  const uintptr_t A = 0x7500'0000'0000ull, W = 0x7600'0000'0000ull, H = 0x7700'0000'0000ull;
+  auto ptr = [](uintptr_t a) { return reinterpret_cast<void *>(a); };
+  fake_block(A, 1 << 20, 0);
+  fake_block(W, 1 << 20, 0);
+  fake_block(H, 4096, 0, true);
+  // four writes: a short head chunk and two packets; an empty one with finish; an empty one without (no
+  // packet); 65 537 bytes on the grid with finish
+  auto fresh = [&] {
+    std::vector<TestEntry> w(4);
+    std::memset(w.data(), 0, w.size() * sizeof(TestEntry));
+    w[0] = TestEntry{ptr(A), 65536, 1, 10, 0, 0, ptr(W), 70000, 9, 9, 9};
+    w[1] = TestEntry{nullptr, 0, 0, 20, 1, 0, ptr(W + 100000), 100, 9, 9, 9};
+    w[2] = TestEntry{nullptr, 0, 5, 30, 0, 0, ptr(W + 100200), 0, 9, 9, 9};
+    w[3] = TestEntry{ptr(A + 200000), 65537, 512, 40, 1, 0, ptr(W + 200000), 70000, 9, 9, 9};
+    return w;
+  };
+  std::vector<TestEntry> w = fresh();
+  const uint64_t hb = hdfs_crc32c::outpkt::out_header_bytes(2);
+  // the list and the arguments
+  Counts c;
+  CHECK(count_batch(w.data(), 6, 5, 2, 2, c) == HDFS_CRC32C_EINVAL && err_is("6 writes, at most 5 in one call"));
+  CHECK(w[0].npkts == 9);  // nothing written yet
+  CHECK(count_batch<TestEntry>(nullptr, 1, 5, 2, 2, c) == HDFS_CRC32C_EINVAL && err_is("null writes"));
+  CHECK(count_batch<TestEntry>(nullptr, 0, 5, 2, 2, c) == 0 && c.chunks == 0 && c.packets == 0);
+  w[2].offset_in_block = -1;
+  CHECK(count_batch(w.data(), 4, 5, 2, 2, c) == HDFS_CRC32C_EINVAL && err_is("entry 2: negative block offset"));
+  for (const TestEntry &e : w) CHECK(e.wire_len == 0 && e.npkts == 0 && e.first_pkt == 0);  // zeroed ahead of any refusal
+  CHECK(count_batch(w.data(), 4, 5, 3, 2, c) == HDFS_CRC32C_EINVAL && err_is("entry 0: proto must be 1 or 2"));
+  // the counts in closed form: 511 + 65025 bytes are 1 + 128 chunks in 1 + 1 packets; finish alone is a packet;
+  // 65537 bytes on the grid are 129 chunks in 2 packets, and finish
+  w = fresh();
+  c = Counts{};
+  CHECK(count_batch(w.data(), 4, 5, 2, 2, c) == 0 && c.chunks == 129 + 0 + 0 + 129 && c.packets == 2 + 1 + 0 + 3);
+  // the walk fills every entry's out fields before the library judges the totals
+  {
+    Batch B;
+    CHECK(test_layout_batch(w.data(), 4, 5, B) == HDFS_CRC32C_EINVAL && err_is("too many packets"));
+    CHECK(w[0].npkts == 2 && w[1].npkts == 1 && w[2].npkts == 0 && w[3].npkts == 3);
+    CHECK(w[0].first_pkt == 0 && w[1].first_pkt == 2 && w[2].first_pkt == 3 && w[3].first_pkt == 3);
+    CHECK(w[0].wire_len == 65536 + 2 * hb + 4 * 129 && w[1].wire_len == hb && w[2].wire_len == 0);
+    CHECK(B.npkts == 6 && B.nchunks == 258 && B.entries == 3 && B.wire_bytes == w[0].wire_len + hb + w[3].wire_len);
+    // the _layout entry point: the totals are written even when the layout is refused
+    TestTotals t;
+    std::memset(&t, 0xEE, sizeof(t));
+    std::vector<TestEntry> w2 = fresh();
+    CHECK(layout_totals(&t, [&](Batch &b) { return test_layout_batch(w2.data(), 4, 5, b); }) == HDFS_CRC32C_EINVAL);
+    CHECK(t.npkts == 6 && t.nchunks == 258 && t.wire_bytes == B.wire_bytes && t.table_entries == 3);
+    CHECK(layout_totals(&t, [&](Batch &b) { return test_layout_batch(w2.data(), 4, 6, b); }) == 0 && t.npkts == 6);
+    CHECK(layout_totals(static_cast<TestTotals *>(nullptr), [&](Batch &) { return 0; }) == HDFS_CRC32C_EINVAL);
+    CHECK(err_is("null out"));
+  }
+  Batch B;
+  CHECK(test_layout_batch(w.data(), 4, 6, B) == 0);
+  // the records: every write's at its first_pkt
+  {
+    std::vector<hdfs_crc32c_out_packet> pk(6);
+    std::memset(pk.data(), 0xEE, pk.size() * sizeof(pk[0]));
+    fill_batch_records(w.data(), B, pk.data());
+    CHECK(pk[0].seqno == 10 && pk[1].seqno == 11 && pk[2].seqno == 20 && pk[3].seqno == 40 && pk[5].seqno == 42);
+    CHECK(pk[0].data_len == 511 && pk[2].last == 1 && pk[2].data_len == 0 && pk[5].last == 1 && pk[4].hdr_off);
+  }
+  // a call that has stream buffers: all or none
+  CHECK(count_wires(w.data(), 4) == 4 && count_wires(w.data(), 0) == 0);
+  CHECK(check_entries(w.data(), 4, 4, B, nullptr, 0) == 0);
+  w[2].wire = w[3].wire = nullptr;
+  CHECK(count_wires(w.data(), 4) == 2 && check_entries(w.data(), 4, 2, B, nullptr, 0) == HDFS_CRC32C_EINVAL);
+  CHECK(err_is("entry 2: wire is NULL, entry 0's is not (every wire NULL is a size query)"));  // the first that differs
+  w = fresh();
+  w[0].wire = w[1].wire = nullptr;
+  CHECK(test_layout_batch(w.data(), 4, 6, B = Batch{}) == 0 && count_wires(w.data(), 4) == 2);
+  CHECK(check_entries(w.data(), 4, 2, B, nullptr, 0) == HDFS_CRC32C_EINVAL);
+  CHECK(err_is("entry 2: wire is set, entry 0's is not (every wire NULL is a size query)"));
+  // every entry's own room, in entry order and data first
+  w = fresh();
+  CHECK(test_layout_batch(w.data(), 4, 6, B = Batch{}) == 0);
+  char want[256];
+  w[3].data = nullptr;
+  w[1].wire_cap = hb - 1;
+  std::snprintf(want, sizeof(want), "entry 1: %llu stream bytes, room for %llu", (unsigned long long)hb, (unsigned long long)hb - 1);
+  CHECK(check_entries(w.data(), 4, 4, B, nullptr, 0) == HDFS_CRC32C_EINVAL && err_is(want));
+  w[1].wire_cap = hb;
+  CHECK(check_entries(w.data(), 4, 4, B, nullptr, 0) == HDFS_CRC32C_EINVAL && err_is("entry 3: null data with 65537 bytes"));
+  w[3].data = ptr(A + 200000);
+  w[3].wire_cap = w[3].wire_len - 1;
+  std::snprintf(want, sizeof(want), "entry 3: %llu stream bytes, room for %llu", (unsigned long long)w[3].wire_len,
+                (unsigned long long)w[3].wire_len - 1);
+  CHECK(check_entries(w.data(), 4, 4, B, nullptr, 0) == HDFS_CRC32C_EINVAL && err_is(want));
+  w[3].wire_cap = w[3].wire_len;
+  std::vector<hdfs_crc32c_out_packet> pk(6);
+  CHECK(check_entries(w.data(), 4, 4, B, pk.data(), 6) == 0 && check_entries(w.data(), 4, 4, B, nullptr, 0) == 0);
+  CHECK(check_entries(w.data(), 4, 4, B, pk.data(), 5) == HDFS_CRC32C_EINVAL);
+  CHECK(err_is("entry 3: its records end at 6 of 6, room for 5"));
+  CHECK(check_entries(w.data(), 4, 4, B, pk.data(), 1) == HDFS_CRC32C_EINVAL);
+  CHECK(err_is("entry 0: its records end at 2 of 6, room for 1"));
+  // where the buffers lie: two allocations, asked about once each; the entries without bytes are not asked about
+  F.n.clear();
+  CHECK(check_batch_places(w.data(), 4, 0) == 0);
+  CHECK(F.n["hipPointerGetAttributes"] == 2 && F.n["hipMemGetAddressRange"] == 2);
+  w[2].wire = ptr(uintptr_t(0x10));  // no stream bytes: any address
+  CHECK(check_batch_places(w.data(), 4, 0) == 0);
+  w[3].data = ptr(H);
+  std::snprintf(want, sizeof(want), "entry 3: data: %p is not device memory", ptr(H));
+  CHECK(check_batch_places(w.data(), 4, 0) == HDFS_CRC32C_EINVAL && err_is(want));
+  w[3].data = ptr(A + (1 << 20) - 65536);
+  std::snprintf(want, sizeof(want), "entry 3: data: 65537 bytes at %p run past the end of their device allocation", w[3].data);
+  CHECK(check_batch_places(w.data(), 4, 0) == HDFS_CRC32C_EINVAL && err_is(want));
+  w[3].data = ptr(A + 200000);
+  w[1].wire = ptr(W + (1 << 20) - (hb - 1));
+  std::snprintf(want, sizeof(want), "entry 1: wire: %llu bytes at %p run past the end of their device allocation",
+                (unsigned long long)hb, w[1].wire);
+  CHECK(check_batch_places(w.data(), 4, 0) == HDFS_CRC32C_EINVAL && err_is(want));
+  w[1].wire = ptr(W + w[0].wire_len - 1);
+  CHECK(check_batch_places(w.data(), 4, 0) == HDFS_CRC32C_EINVAL && err_is("entry 1: wire overlaps the wire of entry 0"));
+  w[1].wire = ptr(W + w[0].wire_len);  // touching
+  CHECK(check_batch_places(w.data(), 4, 0) == 0);
+  w[3].wire = ptr(A + 65535);
+  CHECK(check_batch_places(w.data(), 4, 0) == HDFS_CRC32C_EINVAL && err_is("entry 3: wire overlaps the data of entry 0"));
+  w[3].wire = ptr(A + 65536);
+  CHECK(check_batch_places(w.data(), 4, 0) == 0);  // behind entry 0's data, ahead of its own
+  w[3].wire = ptr(W + 200000);
+  w[3].data = w[0].data;  // two writes of the same bytes
+  CHECK(check_batch_places(w.data(), 4, 0) == 0);
+
+  // a gather write: the fragments and the stream (companion_support.h's check_places)
+  hdfs_crc32c_iovec iov[4] = {{ptr(A), 100}, {nullptr, 0}, {ptr(H), 0}, {ptr(A + 50), 100}};
+  F.n.clear();
+  CHECK(check_places(iov, 4, ptr(W), 300, 0) == 0 && F.n["hipPointerGetAttributes"] == 2);
+  CHECK(check_places(iov, 4, ptr(A + 150), 300, 0) == 0);  // touching the last fragment
+  CHECK(check_places(iov, 4, ptr(A + 149), 300, 0) == HDFS_CRC32C_EINVAL && err_is("fragment 3 and wire overlap"));
+  CHECK(check_places(iov, 4, ptr(A + 99), 1, 0) == HDFS_CRC32C_EINVAL && err_is("fragment 0 and wire overlap"));
+  CHECK(check_places(iov, 4, ptr(W + (1 << 20) - 299), 300, 0) == HDFS_CRC32C_EINVAL);
+  std::snprintf(want, sizeof(want), "wire: 300 bytes at %p run past the end of their device allocation", ptr(W + (1 << 20) - 299));
+  CHECK(err_is(want));
+  iov[2].len = 8;
+  std::snprintf(want, sizeof(want), "fragment 2: data: %p is not device memory", ptr(H));
+  CHECK(check_places(iov, 4, ptr(W), 300, 0) == HDFS_CRC32C_EINVAL && err_is(want));
+  F.blocks.erase(A);
+  F.blocks.erase(W);
   F.blocks.erase(H);
 }
 
@@ -625,10 +1154,15 @@ int main() {
   test_engine_device();
   test_buffers();
   test_scratch();
+  test_timing_events();
+  test_table_pair();
+  test_fused_state();
   test_placement();
+  test_overlaps();
+  test_batch_front_end();
   test_args_and_grid();
   test_tail_and_run();
-  CHECK(F.blocks.empty() && F.streams == 0 && F.wrong_device_frees == 0 && F.sticky == hipSuccess);
+  CHECK(F.blocks.empty() && F.streams == 0 && F.events == 0 && F.wrong_device_frees == 0 && F.sticky == hipSuccess);
   CHECK(F.plans_destroyed - destroyed == 8);  // once for every call above that was given a plan
   std::printf("%d failures\n", g_fail);
   return g_fail ? 1 : 0;

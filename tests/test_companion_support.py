@@ -1,13 +1,18 @@
-"""The host support the four companion libraries share
+"""The host support the eight companion libraries share
 (hadoofus_amd/csrc/companion_support.h; grid_segments and timed_frame_run of
-wire_layout.h), on the CPU: tests/consumer/companion_selftest.cpp defines a
-fake HIP runtime and a fake engine that count and log every call and can be
-told to fail, and is built with ASan/UBSan against the ROCm headers alone (it
-is not linked to the runtime).  It covers the error and lifetime paths the GPU
-tests cannot reach -- failed allocations and streams, a change of the engine's
-device -- and pins the runtime calls of a warm call: none from the buffers and
-the scratch, one attributes and one range query per allocation, and the exact
-sequence of the frame run."""
+wire_layout.h; the fused libraries' device state of wire_fused_host.h; the
+batch front end of wire_batch_layout.h), on the CPU:
+tests/consumer/companion_selftest.cpp defines a fake HIP runtime and a fake
+engine that count and log every call and can be told to fail, and is built
+with ASan/UBSan against the ROCm headers alone (it is not linked to the
+runtime).  It covers the error and lifetime paths the GPU tests cannot reach
+-- failed allocations, streams and events, a failing kernel preparation, a
+change of the engine's device -- and pins the runtime calls of a warm call:
+none from the buffers, the table pair, the events, the fused state and the
+scratch, one attributes and one range query per allocation, and the exact
+sequence of the frame run.  The overlap sweep of a batch's buffers is checked
+against a scan of every pair, over every small batch and a few thousand random
+ones."""
 import os
 import subprocess
 

@@ -285,7 +285,11 @@ def test_sources_hold_no_plan_call_and_no_polynomial():
             assert poly not in src.lower(), (f, poly)
     host = open(os.path.join(build.CSRC, "wire_fused_batch.cpp")).read()
     assert '#include "wire_layout.h"' in host and '#include "wire_fused_tables.h"' in host
-    assert "build_layout(" in host and "fill_records(" in host and "plan_out_packets(" not in host
+    # the batch front end, shared with the two-pass batch library, walks the writes with them
+    front = open(os.path.join(build.CSRC, "wire_batch_layout.h")).read()
+    assert '#include "wire_batch_layout.h"' in host and '#include "wire_layout.h"' in front
+    assert "build_layout(" in front and "fill_records(" in front and "plan_out_packets(" not in host + front
+    assert not re.search(r"^\w[\w ]*\b(build_layout|fill_records)\(", host + front, flags=re.M)  # and defines neither
     assert "put_header_proto" not in host and "hadoofus_wire_batch.h" not in host
     hdr = open(os.path.join(ROOT, "include", "hadoofus_wire_fused_batch.h")).read()
     assert '#include "hadoofus_wire_batch.h"' not in hdr and '#include "hadoofus_wire_fused.h"' not in hdr
