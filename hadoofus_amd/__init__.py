@@ -21,7 +21,9 @@ framing kernel (include/hadoofus_wire_fused.h), in libhadoofus_wire_fused.so
 (include/hadoofus_wire_fused_batch.h) in libhadoofus_wire_fused_batch.so
 (wire_fused_batch.py); a write held in a list of device buffers made that way
 (include/hadoofus_wirev_fused.h) in libhadoofus_wirev_fused.so
-(wirev_fused.py).
+(wirev_fused.py); the streams of a batch of such writes in one launch
+(include/hadoofus_wirev_fused_batch.h) in libhadoofus_wirev_fused_batch.so
+(wirev_fused_batch.py).
 """
 from .abi import (  # noqa: F401
     LIB_PATH, bind_product, bind_diag, CSUM_NULL, CSUM_CRC32, CSUM_CRC32C, ERR_BAD_CHECKSUM, ERR_CRC_LEN,
@@ -43,5 +45,6 @@ from .wirev import compose_wire as compose_wire_iov, layout as wirev_layout  # n
 from .wire_fused import compose_wire as compose_wire_fused  # noqa: F401  (binds nothing until first use)
 from .wire_fused_batch import compose as compose_wire_fused_batch  # noqa: F401  (binds nothing until first use)
 from .wirev_fused import compose_wirev_fused, layout as wirev_fused_layout  # noqa: F401  (binds nothing until first use)
+from .wirev_fused_batch import compose as compose_wirev_fused_batch, layout as wirev_fused_batch_layout  # noqa: F401  (binds nothing until first use)
 
 __all__ = [n for n in dir() if not n.startswith("_")]

@@ -40,6 +40,14 @@ and export map: the same round over the packets of a write held in device
 fragments, found through a fragment table with the lookup of
 wirev_fused_lookup.h.  It compiles neither the gather layout nor the gather
 kernel of the gather libraries.
+
+A ninth companion, libhadoofus_wirev_fused_batch.so
+(include/hadoofus_wirev_fused_batch.h), is built the same way from its own
+sources and export map: the same round over the packets of a batch of writes
+held in device fragments, with both lookups and what connects them
+(wirev_fused_batch_lookup.h), the seamed round of wirev_fused_internal.h and
+the batch front end of wire_batch_layout.h.  It compiles neither the gather
+layout nor the gather kernel of the gather libraries either.
 """
 import os
 import subprocess
@@ -100,6 +108,14 @@ WIREV_FUSED_HEADERS = ["wirev_fused_internal.h", "wirev_fused_lookup.h", "wire_f
                        "wire_fused_tables.h", "wire_fused_host.h", "wire_internal.h", "wire_layout.h",
                        "companion_support.h", "crc32c_outpkt.h", "crc32c_tables.h", "wirev_fused_exports.map"]
 WIREV_FUSED_PUBLIC = ["hadoofus_wirev_fused.h", "hadoofus_crc32c.h"]
+WIREV_FUSED_BATCH_LIB = os.path.join(LIBDIR, "libhadoofus_wirev_fused_batch.so")
+WIREV_FUSED_BATCH_SOURCES = ["wirev_fused_batch_kernels.hip", "wirev_fused_batch.cpp"]
+WIREV_FUSED_BATCH_HEADERS = ["wirev_fused_batch_internal.h", "wirev_fused_batch_lookup.h", "wirev_fused_internal.h",
+                             "wirev_fused_lookup.h", "wire_fused_batch_lookup.h", "wire_fused_round.h",
+                             "wire_fused_crc.h", "wire_fused_tables.h", "wire_fused_host.h", "wire_internal.h",
+                             "wire_layout.h", "wire_batch_layout.h", "companion_support.h", "crc32c_outpkt.h",
+                             "crc32c_tables.h", "wirev_fused_batch_exports.map"]
+WIREV_FUSED_BATCH_PUBLIC = ["hadoofus_wirev_fused_batch.h", "hadoofus_crc32c.h"]
 ARCH = os.environ.get("HADOOFUS_OFFLOAD_ARCH", "gfx950")
 
 
@@ -140,8 +156,8 @@ def _companion_cmd(out, sources, exports):
 def build(force=False, verbose=False, diag=True):
     """Build the release library (and, with diag=True, the diagnostic one,
     in parallel), then the MD5CRC, gather-write, wire-stream, wire-batch,
-    gather-wire, fused-wire, fused-wire-batch and fused-gather-wire companions
-    (in parallel).
+    gather-wire, fused-wire, fused-wire-batch, fused-gather-wire and
+    fused-gather-wire-batch companions (in parallel).
     Returns the release library's path."""
     os.makedirs(LIBDIR, exist_ok=True)
     jobs = []
@@ -170,7 +186,9 @@ def build(force=False, verbose=False, diag=True):
             (WIRE_FUSED_BATCH_LIB, WIRE_FUSED_BATCH_SOURCES, WIRE_FUSED_BATCH_HEADERS, WIRE_FUSED_BATCH_PUBLIC,
              "wire_fused_batch_exports.map"),
             (WIREV_FUSED_LIB, WIREV_FUSED_SOURCES, WIREV_FUSED_HEADERS, WIREV_FUSED_PUBLIC,
-             "wirev_fused_exports.map")):
+             "wirev_fused_exports.map"),
+            (WIREV_FUSED_BATCH_LIB, WIREV_FUSED_BATCH_SOURCES, WIREV_FUSED_BATCH_HEADERS, WIREV_FUSED_BATCH_PUBLIC,
+             "wirev_fused_batch_exports.map")):
         if force or _stale(out, sources, headers, public, [LIB]):
             cmd = _companion_cmd(out + ".tmp", sources, exports)
             if verbose:

@@ -1,5 +1,5 @@
-// Host support shared by the eight companion libraries of
-// libhadoofus_crc32c.so (md5crc.cpp, writev.cpp and the six wire-stream
+// Host support shared by the nine companion libraries of
+// libhadoofus_crc32c.so (md5crc.cpp, writev.cpp and the seven wire-stream
 // libraries wire*.cpp): the last-error text, the engine's device, grow-only
 // buffers, a device table with its pinned staging twin, scratch bound to a
 // device with the two events of a timing call, where a pointer lives, the

@@ -1,10 +1,13 @@
-// Host side shared by the two batch libraries (wire_batch.cpp,
-// wire_fused_batch.cpp): everything a batch call does before it takes its
-// lock.  The layout of every entry and the totals, the records, the argument
-// checks of a call that has stream buffers and where those buffers lie.  One
-// definition, included by both, templated on the public entry struct (the two
-// are field for field the same).  Each library keeps its own limits and the
-// order in which it judges them.  No kernel file includes it.
+// Host side shared by the batch libraries (wire_batch.cpp,
+// wire_fused_batch.cpp, wirev_fused_batch.cpp): everything a batch call does
+// before it takes its lock.  The layout of every entry and the totals, the
+// records, the argument checks of a call that has stream buffers and where
+// those buffers lie.  One definition, included by all, templated on the entry
+// struct (the first two libraries' public ones are field for field the same;
+// the gather batch library lays out a private entry of that shape whose len is
+// the sum of a write's fragments and checks its fragments' places itself).
+// Each library keeps its own limits and the order in which it judges them.  No
+// kernel file includes it.
 #ifndef HADOOFUS_WIRE_BATCH_LAYOUT_H
 #define HADOOFUS_WIRE_BATCH_LAYOUT_H
 
@@ -157,20 +160,33 @@ struct Span {
   uint32_t wire;     // 1: a wire range
 };
 
-inline int check_overlaps(std::vector<Span> &v) {
-  std::sort(v.begin(), v.end(), [](const Span &a, const Span &b) {
-    return a.lo != b.lo ? a.lo < b.lo : (a.wire != b.wire ? a.wire > b.wire : a.k < b.k);
-  });
+// The sweep's order; a caller with very many spans may hand them over in it.
+inline bool span_before(const Span &a, const Span &b) {
+  return a.lo != b.lo ? a.lo < b.lo : (a.wire != b.wire ? a.wire > b.wire : a.k < b.k);
+}
+
+// hit_wire / hit_other (may be NULL): on a refusal, the wire range and the
+// range it overlaps, for a caller whose data ranges are more than one per
+// entry and who names the one at fault.
+inline int check_overlaps(std::vector<Span> &v, Span *hit_wire = nullptr, Span *hit_other = nullptr) {
+  if (!std::is_sorted(v.begin(), v.end(), span_before)) std::sort(v.begin(), v.end(), span_before);
+  const auto hit = [&](const Span &wire, const Span &other) {
+    if (hit_wire) *hit_wire = wire;
+    if (hit_other) *hit_other = other;
+  };
   const Span *far_w = nullptr, *far_d = nullptr;
   for (const Span &s : v) {
     // every span ahead of s starts at or below s.lo: it overlaps s iff it ends behind s.lo
     if (far_w && far_w->hi > s.lo) {
       const uint32_t a = std::max(far_w->k, s.k), b = std::min(far_w->k, s.k);
+      hit(*far_w, s);
       return s.wire ? fail(HDFS_CRC32C_EINVAL, "entry %u: wire overlaps the wire of entry %u", a, b)
                     : fail(HDFS_CRC32C_EINVAL, "entry %u: wire overlaps the data of entry %u", far_w->k, s.k);
     }
-    if (s.wire && far_d && far_d->hi > s.lo)
+    if (s.wire && far_d && far_d->hi > s.lo) {
+      hit(s, *far_d);
       return fail(HDFS_CRC32C_EINVAL, "entry %u: wire overlaps the data of entry %u", s.k, far_d->k);
+    }
     const Span *&far = s.wire ? far_w : far_d;
     if (!far || s.hi > far->hi) far = &s;
   }

@@ -1,8 +1,8 @@
-// Host side shared by the three fused wire-stream libraries (wire_fused.cpp,
-// wire_fused_batch.cpp, wirev_fused.cpp): what each keeps on the engine's
-// device once it has been used there, and how a call picks its table half and
-// its grid.  One definition, included by all three; no kernel file includes
-// it.
+// Host side shared by the four fused wire-stream libraries (wire_fused.cpp,
+// wire_fused_batch.cpp, wirev_fused.cpp, wirev_fused_batch.cpp): what each
+// keeps on the engine's device once it has been used there, and how a call
+// picks its table half and its grid.  One definition, included by all four; no
+// kernel file includes it.
 #ifndef HADOOFUS_WIRE_FUSED_HOST_H
 #define HADOOFUS_WIRE_FUSED_HOST_H
 

@@ -1,5 +1,6 @@
-// Host side shared by the six wire-stream libraries (wire.cpp, wire_batch.cpp,
-// wirev.cpp, wire_fused.cpp, wire_fused_batch.cpp, wirev_fused.cpp): the
+// Host side shared by the seven wire-stream libraries (wire.cpp, wire_batch.cpp,
+// wirev.cpp, wire_fused.cpp, wire_fused_batch.cpp, wirev_fused.cpp,
+// wirev_fused_batch.cpp): the
 // layout of one write's stream, its packet records, the compute-plan segments
 // of its chunk grid (the two-pass libraries') and the timed frame run.  One
 // definition, included by all.  What every companion library shares (last
