@@ -126,10 +126,21 @@ typedef struct hdfs_crc32c_plan hdfs_crc32c_plan;
 int hdfs_crc32c_plan_create(hdfs_crc32c_plan **plan, int mode,
     const hdfs_crc32c_segment *segs, size_t nseg);
 /* Enqueue one pass over every chunk of every segment on `stream`
- * (graph-capturable: no allocation or synchronisation inside). */
+ * (graph-capturable: no allocation or synchronisation inside).  A plan may
+ * be executed any number of times.  Each execute of a verify plan starts
+ * from cleared results (the clearing is part of what is enqueued, so also of
+ * a captured graph) and writes every bitmap byte of every segment, the bytes
+ * of tiles without a bad chunk as 0.  A plan owns ONE set of result words
+ * and one pool counter: its executes must be ordered on one stream at a time
+ * (several back to back on one stream are; two streams, or two threads,
+ * need a plan each). */
 int hdfs_crc32c_plan_execute(hdfs_crc32c_plan *plan, void *stream);
 /* Verify plans: wait for the stream and return the first bad chunk of each
- * segment (UINT32_MAX if none) and the total number of bad chunks. */
+ * segment (UINT32_MAX if none) and the total number of bad chunks -- those of
+ * the last execute completed on `stream`, which must be the stream the plan
+ * was executed on (the call waits for no other).  At most min(nseg, the
+ * plan's segments) words are written; first_bad and mismatches may each be
+ * NULL.  A compute plan has no results (EINVAL). */
 int hdfs_crc32c_plan_results(hdfs_crc32c_plan *plan, void *stream,
     uint32_t *first_bad, size_t nseg, uint64_t *mismatches);
 /* Optional device-side timing of the tiled kernel (HIP events recorded on
