@@ -65,50 +65,57 @@ DIAG_SOURCES = SOURCES + ["crc32c_probes.hip"]
 HEADERS = ["crc32c_internal.h", "crc32c_tables.h", "crc32c_packets.h", "crc32c_engine.h", "crc32c_frame.h",
            "crc32c_hostpin.h", "crc32c_diag_ep.h", "crc32c_deal.h", "crc32c_outpkt.h", "exports.map"]
 PUBLIC = ["hadoofus_crc32c.h", "crc32c.h", "hadoofus_crc32c_diag.h"]
-MD5CRC_LIB = os.path.join(LIBDIR, "libhadoofus_md5crc.so")
+
+
+def companion_lib(stem):
+    """The companion library of that stem: libhadoofus_<stem>.so beside the release library."""
+    return os.path.join(LIBDIR, f"libhadoofus_{stem}.so")
+
+
+MD5CRC_LIB = companion_lib("md5crc")
 MD5CRC_SOURCES = ["md5crc_kernels.hip", "md5crc.cpp"]
 MD5CRC_HEADERS = ["md5_core.h", "md5crc_internal.h", "companion_support.h", "md5crc_exports.map"]
 MD5CRC_PUBLIC = ["hadoofus_md5crc.h", "hadoofus_crc32c.h"]
-WRITEV_LIB = os.path.join(LIBDIR, "libhadoofus_writev.so")
+WRITEV_LIB = companion_lib("writev")
 WRITEV_SOURCES = ["writev_kernels.hip", "writev.cpp"]
 WRITEV_HEADERS = ["writev_internal.h", "writev_layout.h", "crc32c_outpkt.h", "crc32c_tables.h",
                   "companion_support.h", "writev_exports.map"]
 WRITEV_PUBLIC = ["hadoofus_writev.h", "hadoofus_crc32c.h"]
-WIRE_LIB = os.path.join(LIBDIR, "libhadoofus_wire.so")
+WIRE_LIB = companion_lib("wire")
 WIRE_SOURCES = ["wire_kernels.hip", "wire.cpp"]
 WIRE_HEADERS = ["wire_internal.h", "wire_frame.h", "wire_layout.h", "companion_support.h", "crc32c_outpkt.h",
                 "wire_exports.map"]
 WIRE_PUBLIC = ["hadoofus_wire.h", "hadoofus_crc32c.h"]
-WIRE_BATCH_LIB = os.path.join(LIBDIR, "libhadoofus_wire_batch.so")
+WIRE_BATCH_LIB = companion_lib("wire_batch")
 WIRE_BATCH_SOURCES = ["wire_batch_kernels.hip", "wire_batch.cpp"]
 WIRE_BATCH_HEADERS = ["wire_batch_internal.h", "wire_internal.h", "wire_frame.h", "wire_layout.h",
                       "wire_batch_layout.h", "companion_support.h", "crc32c_outpkt.h", "wire_batch_exports.map"]
 WIRE_BATCH_PUBLIC = ["hadoofus_wire_batch.h", "hadoofus_crc32c.h"]
-WIREV_LIB = os.path.join(LIBDIR, "libhadoofus_wirev.so")
+WIREV_LIB = companion_lib("wirev")
 WIREV_SOURCES = ["wirev_kernels.hip", "writev_kernels.hip", "wirev.cpp"]
 WIREV_HEADERS = ["wirev_internal.h", "wire_internal.h", "wire_frame.h", "wire_layout.h", "writev_internal.h",
                  "writev_layout.h", "companion_support.h", "crc32c_outpkt.h", "crc32c_tables.h", "wirev_exports.map"]
 WIREV_PUBLIC = ["hadoofus_wirev.h", "hadoofus_writev.h", "hadoofus_crc32c.h"]
-WIRE_FUSED_LIB = os.path.join(LIBDIR, "libhadoofus_wire_fused.so")
+WIRE_FUSED_LIB = companion_lib("wire_fused")
 WIRE_FUSED_SOURCES = ["wire_fused_kernels.hip", "wire_fused.cpp"]
 WIRE_FUSED_HEADERS = ["wire_fused_internal.h", "wire_fused_round.h", "wire_fused_crc.h", "wire_fused_tables.h",
                       "wire_fused_host.h", "wire_internal.h", "wire_layout.h", "companion_support.h", "crc32c_outpkt.h", "crc32c_tables.h",
                       "wire_fused_exports.map"]
 WIRE_FUSED_PUBLIC = ["hadoofus_wire_fused.h", "hadoofus_crc32c.h"]
-WIRE_FUSED_BATCH_LIB = os.path.join(LIBDIR, "libhadoofus_wire_fused_batch.so")
+WIRE_FUSED_BATCH_LIB = companion_lib("wire_fused_batch")
 WIRE_FUSED_BATCH_SOURCES = ["wire_fused_batch_kernels.hip", "wire_fused_batch.cpp"]
 WIRE_FUSED_BATCH_HEADERS = ["wire_fused_batch_internal.h", "wire_fused_batch_lookup.h", "wire_fused_round.h",
                             "wire_fused_crc.h", "wire_fused_tables.h", "wire_fused_host.h", "wire_internal.h",
                             "wire_layout.h", "wire_batch_layout.h", "companion_support.h", "crc32c_outpkt.h", "crc32c_tables.h",
                             "wire_fused_batch_exports.map"]
 WIRE_FUSED_BATCH_PUBLIC = ["hadoofus_wire_fused_batch.h", "hadoofus_crc32c.h"]
-WIREV_FUSED_LIB = os.path.join(LIBDIR, "libhadoofus_wirev_fused.so")
+WIREV_FUSED_LIB = companion_lib("wirev_fused")
 WIREV_FUSED_SOURCES = ["wirev_fused_kernels.hip", "wirev_fused.cpp"]
 WIREV_FUSED_HEADERS = ["wirev_fused_internal.h", "wirev_fused_lookup.h", "wire_fused_round.h", "wire_fused_crc.h",
                        "wire_fused_tables.h", "wire_fused_host.h", "wire_internal.h", "wire_layout.h",
                        "companion_support.h", "crc32c_outpkt.h", "crc32c_tables.h", "wirev_fused_exports.map"]
 WIREV_FUSED_PUBLIC = ["hadoofus_wirev_fused.h", "hadoofus_crc32c.h"]
-WIREV_FUSED_BATCH_LIB = os.path.join(LIBDIR, "libhadoofus_wirev_fused_batch.so")
+WIREV_FUSED_BATCH_LIB = companion_lib("wirev_fused_batch")
 WIREV_FUSED_BATCH_SOURCES = ["wirev_fused_batch_kernels.hip", "wirev_fused_batch.cpp"]
 WIREV_FUSED_BATCH_HEADERS = ["wirev_fused_batch_internal.h", "wirev_fused_batch_lookup.h", "wirev_fused_internal.h",
                              "wirev_fused_lookup.h", "wire_fused_batch_lookup.h", "wire_fused_round.h",
@@ -116,6 +123,19 @@ WIREV_FUSED_BATCH_HEADERS = ["wirev_fused_batch_internal.h", "wirev_fused_batch_
                              "wire_layout.h", "wire_batch_layout.h", "companion_support.h", "crc32c_outpkt.h",
                              "crc32c_tables.h", "wirev_fused_batch_exports.map"]
 WIREV_FUSED_BATCH_PUBLIC = ["hadoofus_wirev_fused_batch.h", "hadoofus_crc32c.h"]
+# Every companion, in build order: (stem, sources, headers, public headers).  Its library is
+# companion_lib(stem), its export map <stem>_exports.map, its bindings hadoofus_amd/<stem>.py.
+COMPANIONS = (
+    ("md5crc", MD5CRC_SOURCES, MD5CRC_HEADERS, MD5CRC_PUBLIC),
+    ("writev", WRITEV_SOURCES, WRITEV_HEADERS, WRITEV_PUBLIC),
+    ("wire", WIRE_SOURCES, WIRE_HEADERS, WIRE_PUBLIC),
+    ("wire_batch", WIRE_BATCH_SOURCES, WIRE_BATCH_HEADERS, WIRE_BATCH_PUBLIC),
+    ("wirev", WIREV_SOURCES, WIREV_HEADERS, WIREV_PUBLIC),
+    ("wire_fused", WIRE_FUSED_SOURCES, WIRE_FUSED_HEADERS, WIRE_FUSED_PUBLIC),
+    ("wire_fused_batch", WIRE_FUSED_BATCH_SOURCES, WIRE_FUSED_BATCH_HEADERS, WIRE_FUSED_BATCH_PUBLIC),
+    ("wirev_fused", WIREV_FUSED_SOURCES, WIREV_FUSED_HEADERS, WIREV_FUSED_PUBLIC),
+    ("wirev_fused_batch", WIREV_FUSED_BATCH_SOURCES, WIREV_FUSED_BATCH_HEADERS, WIREV_FUSED_BATCH_PUBLIC),
+)
 ARCH = os.environ.get("HADOOFUS_OFFLOAD_ARCH", "gfx950")
 
 
@@ -176,21 +196,10 @@ def build(force=False, verbose=False, diag=True):
         os.replace(out + ".tmp", out)
     # the companions link against the release library, so after it is in place
     procs = []
-    for out, sources, headers, public, exports in (
-            (MD5CRC_LIB, MD5CRC_SOURCES, MD5CRC_HEADERS, MD5CRC_PUBLIC, "md5crc_exports.map"),
-            (WRITEV_LIB, WRITEV_SOURCES, WRITEV_HEADERS, WRITEV_PUBLIC, "writev_exports.map"),
-            (WIRE_LIB, WIRE_SOURCES, WIRE_HEADERS, WIRE_PUBLIC, "wire_exports.map"),
-            (WIRE_BATCH_LIB, WIRE_BATCH_SOURCES, WIRE_BATCH_HEADERS, WIRE_BATCH_PUBLIC, "wire_batch_exports.map"),
-            (WIREV_LIB, WIREV_SOURCES, WIREV_HEADERS, WIREV_PUBLIC, "wirev_exports.map"),
-            (WIRE_FUSED_LIB, WIRE_FUSED_SOURCES, WIRE_FUSED_HEADERS, WIRE_FUSED_PUBLIC, "wire_fused_exports.map"),
-            (WIRE_FUSED_BATCH_LIB, WIRE_FUSED_BATCH_SOURCES, WIRE_FUSED_BATCH_HEADERS, WIRE_FUSED_BATCH_PUBLIC,
-             "wire_fused_batch_exports.map"),
-            (WIREV_FUSED_LIB, WIREV_FUSED_SOURCES, WIREV_FUSED_HEADERS, WIREV_FUSED_PUBLIC,
-             "wirev_fused_exports.map"),
-            (WIREV_FUSED_BATCH_LIB, WIREV_FUSED_BATCH_SOURCES, WIREV_FUSED_BATCH_HEADERS, WIREV_FUSED_BATCH_PUBLIC,
-             "wirev_fused_batch_exports.map")):
+    for stem, sources, headers, public in COMPANIONS:
+        out = companion_lib(stem)
         if force or _stale(out, sources, headers, public, [LIB]):
-            cmd = _companion_cmd(out + ".tmp", sources, exports)
+            cmd = _companion_cmd(out + ".tmp", sources, f"{stem}_exports.map")
             if verbose:
                 print(" ".join(cmd), file=sys.stderr)
             procs.append((out, cmd, subprocess.Popen(cmd)))

@@ -8,16 +8,14 @@ when its hdfs_md5crc_abi_version() is not the one these bindings were written
 for.  No compute here and no fallback.
 """
 import ctypes
-import os
 
-from . import abi
-from .abi import CSUM_CRC32C, CRC32CError, Segment, _host, _int, _sz, _u32, _u64, _vp
+from . import abi, companion
+from .abi import CSUM_CRC32C, Segment, _host, _int, _sz, _u32, _u64, _vp
 
-LIB_PATH = os.path.join(os.path.dirname(abi.LIB_PATH), "libhadoofus_md5crc.so")
 ABI_VERSION = 1  # include/hadoofus_md5crc.h HDFS_MD5CRC_ABI_VERSION these bindings are written for
 MD5_LEN = 16
 
-_lib = None
+_lib = None  # the loaded library: None until the first load()
 
 
 class FileChecksumStruct(ctypes.Structure):
@@ -28,13 +26,6 @@ class FileChecksumStruct(ctypes.Structure):
         ("crc_per_block", _u64),
         ("md5", ctypes.c_uint8 * MD5_LEN),
     ]
-
-
-def check_abi(lib):
-    v = lib.hdfs_md5crc_abi_version()
-    if v != ABI_VERSION:
-        raise ImportError(f"md5crc library ABI version {v}, bindings written for {ABI_VERSION}")
-    return lib
 
 
 def bind(lib):
@@ -53,22 +44,15 @@ def bind(lib):
     return check_abi(lib)
 
 
+_so = companion.Library("md5crc", "md5crc", ABI_VERSION, bind)
+LIB_PATH, check_abi, _check = _so.path, _so.check_abi, _so.check
+
+
 def load(path=LIB_PATH):
     """Load the companion library (raises if it was not built)."""
     global _lib
-    if _lib is not None:
-        return _lib
-    abi.load()  # first: the companion links against the product library
-    if not os.path.exists(path):
-        raise ImportError(f"{path} not built; run `python -m hadoofus_amd.build` "
-                          "(or __graft_entry__.build())")
-    _lib = bind(ctypes.CDLL(path))
+    _lib = _so.load(path)
     return _lib
-
-
-def _check(rc):
-    if rc != 0:
-        raise CRC32CError(rc, load().hdfs_md5crc_last_error().decode(errors="replace"))
 
 
 class FileChecksum:

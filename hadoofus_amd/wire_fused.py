@@ -9,28 +9,16 @@ hdfs_wire_fused_abi_version() is not the one these bindings were written for.
 No compute here and no fallback.
 """
 import ctypes
-import os
+from functools import partial
 
-from . import abi
-from .abi import CSUM_CRC32C, PROTO_V2, CRC32CError, OutPacket, _int, _sz, _u64, _vp
+from . import abi, companion
+from .abi import CSUM_CRC32C, PROTO_V2, OutPacket, _int, _sz, _u64, _vp
 
-LIB_PATH = os.path.join(os.path.dirname(abi.LIB_PATH), "libhadoofus_wire_fused.so")
 ABI_VERSION = 1  # include/hadoofus_wire_fused.h HDFS_WIRE_FUSED_ABI_VERSION these bindings are written for
 MAX_GROUPS = 1024  # workgroups HDFS_WIRE_FUSED_TIME_GROUPS accepts
+time_groups = companion.time_groups  # HDFS_WIRE_FUSED_TIME_GROUPS(n)
 
-_lib = None
-
-
-def time_groups(n):
-    """HDFS_WIRE_FUSED_TIME_GROUPS(n)."""
-    return n << 8
-
-
-def check_abi(lib):
-    v = lib.hdfs_wire_fused_abi_version()
-    if v != ABI_VERSION:
-        raise ImportError(f"fused wire library ABI version {v}, bindings written for {ABI_VERSION}")
-    return lib
+_lib = None  # the loaded library: None until the first load()
 
 
 def bind(lib):
@@ -47,35 +35,22 @@ def bind(lib):
     return check_abi(lib)
 
 
+_so = companion.Library("wire_fused", "fused wire", ABI_VERSION, bind)
+LIB_PATH, check_abi, _check = _so.path, _so.check_abi, _so.check
+
+
 def load(path=LIB_PATH):
     """Load the companion library (raises if it was not built)."""
     global _lib
-    if _lib is not None:
-        return _lib
-    abi.load()  # first: the companion links against the product library
-    if not os.path.exists(path):
-        raise ImportError(f"{path} not built; run `python -m hadoofus_amd.build` "
-                          "(or __graft_entry__.build())")
-    _lib = bind(ctypes.CDLL(path))
+    _lib = _so.load(path)
     return _lib
-
-
-def _check(rc):
-    if rc != 0:
-        raise CRC32CError(rc, load().hdfs_wire_fused_last_error().decode(errors="replace"))
 
 
 def packet_records(nbytes, offset_in_block=0, seqno=0, proto=PROTO_V2, ctype=CSUM_CRC32C, finish=False):
     """The size query of hdfs_wire_fused_compose_packets (no GPU).
     -> (wire_len, [packet dicts]), hdr_off counting in the stream."""
-    lib = load()
-    npk, wl = _sz(0), _u64(0)
     args = (None, nbytes, offset_in_block, seqno, proto, ctype, int(finish))  # a size query reads no data
-    _check(lib.hdfs_wire_fused_compose_packets(*args, None, 0, None, 0, ctypes.byref(npk), ctypes.byref(wl), None))
-    arr = (OutPacket * max(1, npk.value))()
-    _check(lib.hdfs_wire_fused_compose_packets(*args, None, 0, arr, npk.value, ctypes.byref(npk), ctypes.byref(wl),
-                                               None))
-    return wl.value, [arr[i].as_dict() for i in range(npk.value)]
+    return companion.compose_packets(_check, partial(load().hdfs_wire_fused_compose_packets, *args))
 
 
 def compose_wire(dptr, nbytes, wire_ptr, wire_cap, offset_in_block=0, seqno=0, proto=PROTO_V2, ctype=CSUM_CRC32C,
@@ -84,14 +59,9 @@ def compose_wire(dptr, nbytes, wire_ptr, wire_cap, offset_in_block=0, seqno=0, p
     device pointer dptr, as one stream at device pointer wire_ptr (wire_cap
     bytes of room).  -> (wire_len, [packet dicts]); packet i's header buffer
     starts at wire_ptr + hdr_off, its data at hdr_off + hdr_len."""
-    lib = load()
-    npk, wl = _sz(0), _u64(0)
     args = (dptr if nbytes else None, nbytes, offset_in_block, seqno, proto, ctype, int(finish))
-    _check(lib.hdfs_wire_fused_compose_packets(*args, None, 0, None, 0, ctypes.byref(npk), ctypes.byref(wl), None))
-    arr = (OutPacket * max(1, npk.value))()
-    _check(lib.hdfs_wire_fused_compose_packets(*args, wire_ptr, wire_cap, arr, npk.value, ctypes.byref(npk),
-                                               ctypes.byref(wl), stream))
-    return wl.value, [arr[i].as_dict() for i in range(npk.value)]
+    return companion.compose_packets(_check, partial(load().hdfs_wire_fused_compose_packets, *args), wire_ptr,
+                                     wire_cap, stream)
 
 
 def fused_time(dptr, nbytes, wire_ptr, wire_cap, offset_in_block=0, proto=PROTO_V2, ctype=CSUM_CRC32C,

@@ -17,23 +17,18 @@ wire_ptr is a raw device pointer or a torch device tensor (its data_ptr() is
 taken; wire_cap then defaults to the tensor's size).
 """
 import ctypes
-import os
 
-from . import abi
-from .abi import CSUM_CRC32C, PROTO_V2, CRC32CError, IoVec, OutPacket, _int, _sz, _u32, _u64, _vp
+from . import abi, companion
+from .abi import CSUM_CRC32C, PROTO_V2, IoVec, OutPacket, _int, _sz, _u32, _u64, _vp
 
-LIB_PATH = os.path.join(os.path.dirname(abi.LIB_PATH), "libhadoofus_wirev_fused_batch.so")
 ABI_VERSION = 1  # include/hadoofus_wirev_fused_batch.h HDFS_WIREV_FUSED_BATCH_ABI_VERSION these bindings are written for
 MAX_WRITES = 65536  # HDFS_WIREV_FUSED_BATCH_MAX_WRITES
 MAX_FRAGS = 1 << 22  # HDFS_WIREV_FUSED_BATCH_MAX_FRAGS
 MAX_GROUPS = 1024  # workgroups HDFS_WIREV_FUSED_BATCH_TIME_GROUPS accepts
+time_groups = companion.time_groups  # HDFS_WIREV_FUSED_BATCH_TIME_GROUPS(n)
+_split = companion.split
 
-_lib = None
-
-
-def time_groups(n):
-    """HDFS_WIREV_FUSED_BATCH_TIME_GROUPS(n)."""
-    return n << 8
+_lib = None  # the loaded library: None until the first load()
 
 
 class BatchWrite(ctypes.Structure):
@@ -55,8 +50,16 @@ class BatchWrite(ctypes.Structure):
     def out(self):
         return {"len": self.len, "wire_len": self.wire_len, "npkts": self.npkts, "first_pkt": self.first_pkt}
 
+    def source(self, w):
+        """-> the IoVec array the entry now points to."""
+        fr = w["frags"]
+        vec = fr if isinstance(fr, ctypes.Array) else companion.iovecs(fr)[0]
+        self.iov = ctypes.cast(vec, ctypes.POINTER(IoVec))
+        self.iovcnt = len(fr) if w["iovcnt"] is None else w["iovcnt"]
+        return vec
 
-class Totals(ctypes.Structure):
+
+class Totals(companion.Record):
     """struct hdfs_wirev_fused_batch_totals."""
     _fields_ = [
         ("npkts", _u64),
@@ -70,16 +73,6 @@ class Totals(ctypes.Structure):
         ("max_frags_per_round", _u32),
         ("reserved", _u32),
     ]
-
-    def as_dict(self):
-        return {f: getattr(self, f) for f, _ in self._fields_ if f != "reserved"}
-
-
-def check_abi(lib):
-    v = lib.hdfs_wirev_fused_batch_abi_version()
-    if v != ABI_VERSION:
-        raise ImportError(f"fused wirev batch library ABI version {v}, bindings written for {ABI_VERSION}")
-    return lib
 
 
 def bind(lib):
@@ -96,79 +89,41 @@ def bind(lib):
     return check_abi(lib)
 
 
+_so = companion.Library("wirev_fused_batch", "fused wirev batch", ABI_VERSION, bind)
+LIB_PATH, check_abi, _check = _so.path, _so.check_abi, _so.check
+
+
 def load(path=LIB_PATH):
     """Load the companion library (raises if it was not built)."""
     global _lib
-    if _lib is not None:
-        return _lib
-    abi.load()  # first: the companion links against the product library
-    if not os.path.exists(path):
-        raise ImportError(f"{path} not built; run `python -m hadoofus_amd.build` "
-                          "(or __graft_entry__.build())")
-    _lib = bind(ctypes.CDLL(path))
+    _lib = _so.load(path)
     return _lib
-
-
-def _check(rc):
-    if rc != 0:
-        raise CRC32CError(rc, load().hdfs_wirev_fused_batch_last_error().decode(errors="replace"))
 
 
 def write(frags=(), wire_ptr=None, wire_cap=None, offset_in_block=0, seqno=0, finish=False, iovcnt=None):
     """One write of a batch, as the dict the functions below take."""
-    wn = None
-    if hasattr(wire_ptr, "data_ptr"):
-        wire_ptr, wn = wire_ptr.data_ptr(), wire_ptr.numel() * wire_ptr.element_size()
-    return dict(frags=frags, wire_ptr=None if wire_ptr is None else int(wire_ptr),
-                wire_cap=(wn or 0) if wire_cap is None else wire_cap, offset_in_block=offset_in_block, seqno=seqno,
-                finish=finish, iovcnt=iovcnt)
+    wire_ptr, wn = companion.ptr(wire_ptr)
+    return dict(frags=frags, wire_ptr=wire_ptr, wire_cap=(wn or 0) if wire_cap is None else wire_cap,
+                offset_in_block=offset_in_block, seqno=seqno, finish=finish, iovcnt=iovcnt)
 
 
 def entries(writes, query=False):
     """The C array of a list of write dicts.  query: wire NULL in every entry.
     -> (array, the IoVec arrays it points to: keep them alive with it)."""
-    arr, keep = (BatchWrite * max(1, len(writes)))(), []
-    for e, w in zip(arr, writes):
-        w = write(**w)
-        fr = w["frags"]
-        if isinstance(fr, ctypes.Array):
-            vec = fr
-        else:
-            vec = (IoVec * max(1, len(fr)))(*[IoVec(p if n else None, n) for p, n in fr])
-        cnt = len(fr) if w["iovcnt"] is None else w["iovcnt"]
-        keep.append(vec)
-        e.iov = ctypes.cast(vec, ctypes.POINTER(IoVec))
-        e.iovcnt = cnt
-        e.offset_in_block = w["offset_in_block"]
-        e.seqno = w["seqno"]
-        e.finish = int(bool(w["finish"]))
-        e.wire = None if query else w["wire_ptr"]
-        e.wire_cap = 0 if query else w["wire_cap"]
-    return arr, keep
+    return companion.entries(writes, query, BatchWrite, write)
 
 
 def layout(writes, proto=PROTO_V2, ctype=CSUM_CRC32C):
     """hdfs_wirev_fused_batch_layout (host only; only the fragments' lengths count).
     -> ([{len, wire_len, npkts, first_pkt} per write], dict of struct hdfs_wirev_fused_batch_totals' fields)."""
-    (arr, _keep), tot = entries(writes, query=True), Totals()
-    _check(load().hdfs_wirev_fused_batch_layout(arr, len(writes), proto, ctype, ctypes.byref(tot)))
-    return [arr[k].out() for k in range(len(writes))], tot.as_dict()
-
-
-def _split(arr, n, recs):
-    return [(arr[k].wire_len, recs[arr[k].first_pkt:arr[k].first_pkt + arr[k].npkts]) for k in range(n)]
+    return companion.batch_layout(_so, load(), writes, proto, ctype, entries, Totals)
 
 
 def packet_records(writes, proto=PROTO_V2, ctype=CSUM_CRC32C):
     """The size query of hdfs_wirev_fused_batch_compose (no GPU; no base is read).
     -> [(wire_len, [packet dicts]) per write], hdr_off counting in the write's
     own stream, data_off in its fragments' concatenation."""
-    lib, n = load(), len(writes)
-    (arr, _keep), npk = entries(writes, query=True), _sz(0)
-    _check(lib.hdfs_wirev_fused_batch_compose(arr, n, proto, ctype, None, 0, ctypes.byref(npk), None))
-    pk = (OutPacket * max(1, npk.value))()
-    _check(lib.hdfs_wirev_fused_batch_compose(arr, n, proto, ctype, pk, npk.value, ctypes.byref(npk), None))
-    return _split(arr, n, [pk[i].as_dict() for i in range(npk.value)])
+    return companion.batch_packet_records(_so, load(), writes, proto, ctype, entries)
 
 
 def compose(writes, proto=PROTO_V2, ctype=CSUM_CRC32C, stream=None):
@@ -176,14 +131,7 @@ def compose(writes, proto=PROTO_V2, ctype=CSUM_CRC32C, stream=None):
     write k's at its wire_ptr.  -> [(wire_len, [packet dicts]) per write];
     packet i's header buffer starts at wire_ptr + hdr_off, its data at hdr_off
     + hdr_len."""
-    lib, n = load(), len(writes)
-    tot = Totals()
-    arr, _keep = entries(writes, query=True)
-    _check(lib.hdfs_wirev_fused_batch_layout(arr, n, proto, ctype, ctypes.byref(tot)))
-    (arr, _keep), npk = entries(writes), _sz(0)
-    pk = (OutPacket * max(1, tot.npkts))()
-    _check(lib.hdfs_wirev_fused_batch_compose(arr, n, proto, ctype, pk, tot.npkts, ctypes.byref(npk), stream))
-    return _split(arr, n, [pk[i].as_dict() for i in range(npk.value)])
+    return companion.batch_compose(_so, load(), writes, proto, ctype, stream, entries, Totals)
 
 
 def fused_batch_time(writes, proto=PROTO_V2, ctype=CSUM_CRC32C, flags=0, iters=10):

@@ -7,20 +7,18 @@ links against it), and refused when its hdfs_writev_abi_version() is not the
 one these bindings were written for.  No compute here and no fallback.
 """
 import ctypes
-import os
 
 import numpy as np
 
-from . import abi
-from .abi import CSUM_CRC32C, PROTO_V2, CRC32CError, IoVec, OutPacket, _host, _int, _sz, _u32, _u64, _vp
+from . import abi, companion
+from .abi import CSUM_CRC32C, PROTO_V2, IoVec, OutPacket, _host, _int, _sz, _u32, _u64, _vp
 
-LIB_PATH = os.path.join(os.path.dirname(abi.LIB_PATH), "libhadoofus_writev.so")
 ABI_VERSION = 1  # include/hadoofus_writev.h HDFS_WRITEV_ABI_VERSION these bindings are written for
 
-_lib = None
+_lib = None  # the loaded library: None until the first load()
 
 
-class LayoutInfo(ctypes.Structure):
+class LayoutInfo(companion.Record):
     """struct hdfs_writev_layout_info."""
     _fields_ = [
         ("total", _u64),
@@ -32,16 +30,6 @@ class LayoutInfo(ctypes.Structure):
         ("max_pieces", _u32),
         ("min_seg_chunks", _u32),
     ]
-
-    def as_dict(self):
-        return {f: getattr(self, f) for f, _ in self._fields_}
-
-
-def check_abi(lib):
-    v = lib.hdfs_writev_abi_version()
-    if v != ABI_VERSION:
-        raise ImportError(f"writev library ABI version {v}, bindings written for {ABI_VERSION}")
-    return lib
 
 
 def bind(lib):
@@ -56,22 +44,15 @@ def bind(lib):
     return check_abi(lib)
 
 
+_so = companion.Library("writev", "writev", ABI_VERSION, bind)
+LIB_PATH, check_abi, _check = _so.path, _so.check_abi, _so.check
+
+
 def load(path=LIB_PATH):
     """Load the companion library (raises if it was not built)."""
     global _lib
-    if _lib is not None:
-        return _lib
-    abi.load()  # first: the companion links against the product library
-    if not os.path.exists(path):
-        raise ImportError(f"{path} not built; run `python -m hadoofus_amd.build` "
-                          "(or __graft_entry__.build())")
-    _lib = bind(ctypes.CDLL(path))
+    _lib = _so.load(path)
     return _lib
-
-
-def _check(rc):
-    if rc != 0:
-        raise CRC32CError(rc, load().hdfs_writev_last_error().decode(errors="replace"))
 
 
 def iovecs(frags):
@@ -109,8 +90,6 @@ def layout(lens, offset_in_block=0):
     """hdfs_writev_layout (host only): how a write of these fragment lengths
     is split between in-place segments and gathered chunks.  -> dict of
     struct hdfs_writev_layout_info's fields."""
-    n = len(lens)
-    arr = (_u64 * max(1, n))(*lens)
-    info = LayoutInfo()
+    (arr, n), info = companion.lengths(lens), LayoutInfo()
     _check(load().hdfs_writev_layout(arr, n, offset_in_block, ctypes.byref(info)))
     return info.as_dict()
