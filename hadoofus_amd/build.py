@@ -48,6 +48,15 @@ held in device fragments, with both lookups and what connects them
 (wirev_fused_batch_lookup.h), the seamed round of wirev_fused_internal.h and
 the batch front end of wire_batch_layout.h.  It compiles neither the gather
 layout nor the gather kernel of the gather libraries either.
+
+The read side has a table of its own, READ_LIBRARIES, with rows of the same
+shape: libhadoofus_read_batch.so (include/hadoofus_read_batch.h) is built with
+the companions, the same way, from its own sources and export map.  It runs the
+fused round the other way (wire_fused_round.h) over the packets of a batch of
+block reads, found with the lookup of wire_fused_batch_lookup.h from the probe
+arithmetic of read_batch_layout.h, and hands what it does not take to the
+release library's hdfs_crc32c_read_packets.  Its bindings are the package
+hadoofus_read beside this one.
 """
 import os
 import subprocess
@@ -136,6 +145,17 @@ COMPANIONS = (
     ("wirev_fused", WIREV_FUSED_SOURCES, WIREV_FUSED_HEADERS, WIREV_FUSED_PUBLIC),
     ("wirev_fused_batch", WIREV_FUSED_BATCH_SOURCES, WIREV_FUSED_BATCH_HEADERS, WIREV_FUSED_BATCH_PUBLIC),
 )
+READ_BATCH_LIB = companion_lib("read_batch")
+READ_BATCH_SOURCES = ["read_batch_kernels.hip", "read_batch.cpp"]
+READ_BATCH_HEADERS = ["read_batch_internal.h", "read_batch_layout.h", "wire_fused_batch_lookup.h", "wire_fused_round.h",
+                      "wire_fused_crc.h", "wire_fused_tables.h", "wire_fused_host.h", "wire_internal.h",
+                      "crc32c_frame.h", "crc32c_outpkt.h", "crc32c_tables.h", "companion_support.h",
+                      "read_batch_exports.map"]
+READ_BATCH_PUBLIC = ["hadoofus_read_batch.h", "hadoofus_crc32c.h"]
+# The read side's libraries, rows as in COMPANIONS; their bindings are hadoofus_read/<stem>.py.
+READ_LIBRARIES = (
+    ("read_batch", READ_BATCH_SOURCES, READ_BATCH_HEADERS, READ_BATCH_PUBLIC),
+)
 ARCH = os.environ.get("HADOOFUS_OFFLOAD_ARCH", "gfx950")
 
 
@@ -177,7 +197,8 @@ def build(force=False, verbose=False, diag=True):
     """Build the release library (and, with diag=True, the diagnostic one,
     in parallel), then the MD5CRC, gather-write, wire-stream, wire-batch,
     gather-wire, fused-wire, fused-wire-batch, fused-gather-wire and
-    fused-gather-wire-batch companions (in parallel).
+    fused-gather-wire-batch companions and the read side's libraries (in
+    parallel).
     Returns the release library's path."""
     os.makedirs(LIBDIR, exist_ok=True)
     jobs = []
@@ -196,7 +217,7 @@ def build(force=False, verbose=False, diag=True):
         os.replace(out + ".tmp", out)
     # the companions link against the release library, so after it is in place
     procs = []
-    for stem, sources, headers, public in COMPANIONS:
+    for stem, sources, headers, public in COMPANIONS + READ_LIBRARIES:
         out = companion_lib(stem)
         if force or _stale(out, sources, headers, public, [LIB]):
             cmd = _companion_cmd(out + ".tmp", sources, f"{stem}_exports.map")

@@ -1,0 +1,15 @@
+"""hadoofus_read -- the read side's batch library, beside hadoofus_amd.
+
+A batch of block reads in one call (include/hadoofus_read_batch.h: the packet
+streams of many block transfers verified and de-framed into device buffers by
+one launch) lives in libhadoofus_read_batch.so, built by hadoofus_amd.build
+beside the product library and loaded on first use (read_batch.py).  A thin
+ctypes mirror of that ABI on hadoofus_amd.companion's loader: no compute here
+and no fallback of its own.  Importing the package loads nothing.
+"""
+from .read_batch import (  # noqa: F401  (binds nothing until first use)
+    ABI_VERSION, LIB_PATH, MAX_ENTRIES, MAX_GROUPS, PATH_FALLBACK, PATH_KERNEL, Entry, entry, read_blocks, time,
+    time_groups,
+)
+
+__all__ = [n for n in dir() if not n.startswith("_")]
