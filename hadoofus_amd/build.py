@@ -57,6 +57,16 @@ block reads, found with the lookup of wire_fused_batch_lookup.h from the probe
 arithmetic of read_batch_layout.h, and hands what it does not take to the
 release library's hdfs_crc32c_read_packets.  Its bindings are the package
 hadoofus_read beside this one.
+
+Positional reads have a third table, PREAD_LIBRARIES, again with rows of that
+shape: libhadoofus_pread_batch.so (include/hadoofus_pread_batch.h) is built
+with the others, the same way, from its own sources and export map.  It runs
+the read batch's round with a windowed store over the packets a batch of
+client reads takes, from the window arithmetic of pread_batch_layout.h (which
+builds on read_batch_layout.h), shares the round's comparisons with the read
+batch library (read_batch_verify.h, compiled into both) and hands what it does
+not take to hdfs_crc32c_read_packets with the entry's window.  Its bindings
+are hadoofus_read/pread_batch.py.
 """
 import os
 import subprocess
@@ -150,11 +160,22 @@ READ_BATCH_SOURCES = ["read_batch_kernels.hip", "read_batch.cpp"]
 READ_BATCH_HEADERS = ["read_batch_internal.h", "read_batch_layout.h", "wire_fused_batch_lookup.h", "wire_fused_round.h",
                       "wire_fused_crc.h", "wire_fused_tables.h", "wire_fused_host.h", "wire_internal.h",
                       "crc32c_frame.h", "crc32c_outpkt.h", "crc32c_tables.h", "companion_support.h",
-                      "read_batch_exports.map"]
+                      "read_batch_verify.h", "read_batch_exports.map"]
 READ_BATCH_PUBLIC = ["hadoofus_read_batch.h", "hadoofus_crc32c.h"]
 # The read side's libraries, rows as in COMPANIONS; their bindings are hadoofus_read/<stem>.py.
 READ_LIBRARIES = (
     ("read_batch", READ_BATCH_SOURCES, READ_BATCH_HEADERS, READ_BATCH_PUBLIC),
+)
+PREAD_BATCH_LIB = companion_lib("pread_batch")
+PREAD_BATCH_SOURCES = ["pread_batch_kernels.hip", "pread_batch.cpp"]
+PREAD_BATCH_HEADERS = ["pread_batch_internal.h", "pread_batch_layout.h", "read_batch_layout.h", "read_batch_verify.h",
+                       "wire_fused_batch_lookup.h", "wire_fused_round.h", "wire_fused_crc.h", "wire_fused_tables.h",
+                       "wire_fused_host.h", "wire_internal.h", "crc32c_frame.h", "crc32c_outpkt.h", "crc32c_tables.h",
+                       "companion_support.h", "pread_batch_exports.map"]
+PREAD_BATCH_PUBLIC = ["hadoofus_pread_batch.h", "hadoofus_crc32c.h"]
+# The positional-read libraries, rows as in COMPANIONS; their bindings are hadoofus_read/<stem>.py.
+PREAD_LIBRARIES = (
+    ("pread_batch", PREAD_BATCH_SOURCES, PREAD_BATCH_HEADERS, PREAD_BATCH_PUBLIC),
 )
 ARCH = os.environ.get("HADOOFUS_OFFLOAD_ARCH", "gfx950")
 
@@ -197,8 +218,8 @@ def build(force=False, verbose=False, diag=True):
     """Build the release library (and, with diag=True, the diagnostic one,
     in parallel), then the MD5CRC, gather-write, wire-stream, wire-batch,
     gather-wire, fused-wire, fused-wire-batch, fused-gather-wire and
-    fused-gather-wire-batch companions and the read side's libraries (in
-    parallel).
+    fused-gather-wire-batch companions, the read side's libraries and the
+    positional-read libraries (in parallel).
     Returns the release library's path."""
     os.makedirs(LIBDIR, exist_ok=True)
     jobs = []
@@ -217,7 +238,7 @@ def build(force=False, verbose=False, diag=True):
         os.replace(out + ".tmp", out)
     # the companions link against the release library, so after it is in place
     procs = []
-    for stem, sources, headers, public in COMPANIONS + READ_LIBRARIES:
+    for stem, sources, headers, public in COMPANIONS + READ_LIBRARIES + PREAD_LIBRARIES:
         out = companion_lib(stem)
         if force or _stale(out, sources, headers, public, [LIB]):
             cmd = _companion_cmd(out + ".tmp", sources, f"{stem}_exports.map")

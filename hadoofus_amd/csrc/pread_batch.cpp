@@ -1,0 +1,280 @@
+// libhadoofus_pread_batch.so: entry points of include/hadoofus_pread_batch.h.
+//
+// A companion of libhadoofus_crc32c.so, not a second engine: the device is
+// the one that library is bound to (hdfs_crc32c_init /
+// hdfs_crc32c_bound_device, its public API) and both share one HIP runtime.
+// Its kernels (pread_batch_kernels.hip) frame and verify the packets the
+// regular entries' reads take and deliver the bytes of their windows; the CRC
+// tables are the fused write libraries' (wire_fused_host.h, built out of
+// crc32c_tables.h).  Every other entry is
+// hdfs_crc32c_read_packets' work, called here after the synchronise: this
+// file holds no walk of its own.  The records of a regular entry follow from
+// its descriptor, cut by the probe to the packets the read takes
+// (pread_batch_layout.h; read_batch_layout.h: packet_of, record_of).
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <mutex>
+#include <vector>
+
+#include "companion_support.h"
+#include "hadoofus_pread_batch.h"
+#include "pread_batch_internal.h"
+#include "pread_batch_layout.h"
+#include "wire_fused_host.h"
+#include "wire_fused_tables.h"
+
+namespace hdfs_pread_batch {
+namespace {
+
+using namespace hdfs_companion;
+
+static_assert(HDFS_PREAD_BATCH_MAX_ENTRIES == kMaxEntries, "the header's limit is the probe's");
+
+// ---- device state -------------------------------------------------------------
+// On the engine's device: the CRC tables and the workgroups of one launch
+// (wire_fused_host.h), set up when the library is first used there and kept;
+// the call's device tables and their pinned twin, grown on demand, never
+// shrunk, kept between calls.  Calls hold g_mu from the tables' upload to the
+// last fallback entry, so one call's tables are never overwritten under its
+// kernels or under the host's reading of them.
+std::mutex g_mu;
+using Fused = hdfs_wire_fused::DeviceState<prepare_unframe_window_batch, kBatchMaxGroups>;
+struct Scratch : DeviceScratch {
+  Fused fused;
+  TablePair tab;
+  std::vector<hdfs_crc32c_packet> recs;  // a fallback entry's records when the caller wants none
+
+  int reserve(int to, size_t tab_bytes) {
+    int rc = bind(to, "stream", [this] {
+      fused.release();
+      tab.release();
+    });
+    if (rc || (rc = fused.setup(to))) return rc;
+    return tab.reserve(tab_bytes, kTableFloor);
+  }
+} g_s;
+
+void clear_outputs(hdfs_pread_batch_entry *e, size_t n) {
+  for (size_t b = 0; b < n; b++) {
+    e[b].consumed = e[b].delivered = e[b].npkts = 0;
+    e[b].rc = 0;
+    e[b].path = HDFS_PREAD_BATCH_PATH_FALLBACK;
+  }
+}
+
+// ---- argument checks that need no device ------------------------------------------
+int check_arguments(hdfs_pread_batch_entry *e, size_t n, int proto, uint32_t chunk_size, int ctype) {
+  if (!e || !n) return fail(HDFS_CRC32C_EINVAL, "no entries");
+  if (n > kMaxEntries)
+    return fail(HDFS_CRC32C_EINVAL, "%zu entries, at most %u in one call", n, unsigned(kMaxEntries));
+  clear_outputs(e, n);
+  if (!packet_args_ok(proto, ctype, 0)) return prefix_fail(HDFS_CRC32C_EINVAL, "entry 0");
+  if (ctype == HDFS_CRC32C_CSUM_NULL)
+    return fail(HDFS_CRC32C_EINVAL, "entry 0: verify + copy-out needs CRC32 or CRC32C");
+  if (!chunk_size) return fail(HDFS_CRC32C_EINVAL, "entry 0: chunk_size 0");
+  for (size_t b = 0; b < n; b++) {
+    if (e[b].len && !e[b].stream) return fail(HDFS_CRC32C_EINVAL, "entry %zu: null stream", b);
+    if (e[b].len && e[b].dst_cap && !e[b].dst) return fail(HDFS_CRC32C_EINVAL, "entry %zu: null destination", b);
+    if (e[b].read_len == HDFS_CRC32C_READ_ALL)
+      return fail(HDFS_CRC32C_EINVAL, "entry %zu: whole payloads (READ_ALL) are hdfs_read_batch_read_blocks' job", b);
+    if (e[b].read_len <= 0)
+      return fail(HDFS_CRC32C_EINVAL, "entry %zu: read_len %lld, a read window has at least one byte", b,
+                  (long long)e[b].read_len);
+  }
+  return HDFS_CRC32C_OK;
+}
+
+// An entry without a stream or without room names no range: the main call
+// answers it without looking at either.
+bool has_ranges(const hdfs_pread_batch_entry &x) { return x.len && x.dst_cap; }
+
+// ---- where the buffers lie -----------------------------------------------------------
+// Every range inside one allocation of device `dev`; no destination overlaps a
+// stream or another destination.  A call may hold 1 024 small reads, so the
+// overlaps are found by one sweep over the ranges sorted by their first byte,
+// not by comparing every pair: a range overlaps an earlier one exactly when it
+// starts below the furthest end met so far, kept apart for the destinations
+// and for the streams (streams may overlap each other).
+struct Span {
+  uintptr_t lo, hi;
+  size_t entry;
+  bool dst;
+};
+
+int check_batch_places(const hdfs_pread_batch_entry *e, size_t n, int dev) {
+  int rc;
+  Allocations al;
+  std::vector<Span> v;
+  v.reserve(2 * n);
+  for (size_t b = 0; b < n; b++) {
+    if (!has_ranges(e[b])) continue;
+    if ((rc = al.check(e[b].stream, e[b].len, dev, "stream")) || (rc = al.check(e[b].dst, e[b].dst_cap, dev, "dst")))
+      return prefix_fail(rc, "entry %zu", b);
+    const uintptr_t s0 = reinterpret_cast<uintptr_t>(e[b].stream), d0 = reinterpret_cast<uintptr_t>(e[b].dst);
+    v.push_back(Span{s0, s0 + uintptr_t(e[b].len), b, false});
+    v.push_back(Span{d0, d0 + uintptr_t(e[b].dst_cap), b, true});
+  }
+  std::sort(v.begin(), v.end(), [](const Span &x, const Span &y) { return x.lo < y.lo; });
+  const Span *far_d = nullptr, *far_s = nullptr;  // the destination and the stream that reach furthest so far
+  for (const Span &c : v) {
+    if (far_d && c.lo < far_d->hi) {
+      if (!c.dst)
+        return fail(HDFS_CRC32C_EINVAL, "entry %zu: dst overlaps the stream of entry %zu", far_d->entry, c.entry);
+      const size_t hi = c.entry > far_d->entry ? c.entry : far_d->entry, lo = c.entry + far_d->entry - hi;
+      return fail(HDFS_CRC32C_EINVAL, "entry %zu: dst overlaps the dst of entry %zu", hi, lo);
+    }
+    if (c.dst && far_s && c.lo < far_s->hi)
+      return fail(HDFS_CRC32C_EINVAL, "entry %zu: dst overlaps the stream of entry %zu", c.entry, far_s->entry);
+    const Span *&far = c.dst ? far_d : far_s;
+    if (!far || c.hi > far->hi) far = &c;
+  }
+  return HDFS_CRC32C_OK;
+}
+
+// ---- an entry handed to the main library ------------------------------------------------
+// Exactly the call of the contract.  Without a record array of the caller's the
+// walk must not be cut, so the library's own array grows until it is not.
+int fallback(hdfs_pread_batch_entry &x, size_t b, int proto, uint32_t chunk_size, int ctype, hdfs_crc32c_packet *pkts,
+             size_t max_pkts) {
+  const hdfs_crc32c_iovec iov{x.dst, x.dst_cap};
+  size_t np = 0;
+  uint64_t used = 0, got = 0;
+  int rc;
+  if (pkts) {
+    rc = hdfs_crc32c_read_packets(x.stream, x.len, proto, chunk_size, ctype, x.client_offset, x.read_len, &iov, 1,
+                                  pkts + b * max_pkts, max_pkts, &np, &used, &got);
+  } else {
+    // a complete framing-clean packet has at least 25 bytes, and one record ends the walk
+    const uint64_t most = x.len / 25u + 2u;
+    uint64_t room = most < 4096u ? most : 4096u;
+    for (;;) {
+      if (g_s.recs.size() < room) g_s.recs.resize(size_t(room));
+      rc = hdfs_crc32c_read_packets(x.stream, x.len, proto, chunk_size, ctype, x.client_offset, x.read_len, &iov, 1,
+                                    g_s.recs.data(), size_t(room), &np, &used, &got);
+      if (rc < 0 || np < room || room >= most) break;
+      room = room * 16u < most ? room * 16u : most;
+    }
+  }
+  x.rc = rc;
+  x.path = HDFS_PREAD_BATCH_PATH_FALLBACK;
+  if (rc < 0) return engine_fail(rc, "read_packets"), prefix_fail(rc, "entry %zu", b);
+  x.npkts = np;
+  x.consumed = used;
+  x.delivered = got;
+  return rc;
+}
+
+// ---- the call -------------------------------------------------------------------------
+// timing == false: the call of hdfs_pread_batch_read.  timing: the same
+// on the library's stream, then both launches alone iters more times between
+// two events (hdfs_pread_batch_time).
+int read_windows(hdfs_pread_batch_entry *e, size_t n, int proto, uint32_t chunk_size, int ctype,
+                 hdfs_crc32c_packet *pkts, size_t max_pkts, void *stream, bool timing, unsigned flags, int iters,
+                 double *ms_per_iter) {
+  if (ms_per_iter) *ms_per_iter = 0;
+  int rc = check_arguments(e, n, proto, chunk_size, ctype);
+  if (rc) return rc;
+  if (timing) {  // decided by the arguments alone, before any device is asked
+    if (iters < 1 || !ms_per_iter) return fail(HDFS_CRC32C_EINVAL, "iters >= 1 and ms_per_iter are needed");
+    if ((rc = Fused::flags_ok(flags))) return rc;
+  }
+  int dev = -1;
+  if ((rc = engine_device(&dev))) return rc;
+  DeviceGuard g(dev);
+  if ((rc = check_batch_places(e, n, dev))) return rc;
+  const Tables T(n);
+  std::lock_guard<std::mutex> lk(g_mu);
+  if ((rc = g_s.reserve(dev, T.bytes)) || (timing && (rc = g_s.timing_events()))) return rc;
+  // the entries, in pinned memory; one without ranges is uploaded empty, so the probe finds it irregular
+  uint8_t *pin = g_s.tab.pin.as<uint8_t>(), *dv = g_s.tab.dev.as<uint8_t>();
+  Entry *in = reinterpret_cast<Entry *>(pin + T.in);
+  for (size_t b = 0; b < n; b++)
+    in[b] = has_ranges(e[b]) ? Entry{static_cast<const uint8_t *>(e[b].stream), e[b].len,
+                                     static_cast<uint8_t *>(e[b].dst), e[b].dst_cap, e[b].client_offset, e[b].read_len}
+                             : Entry{nullptr, 0, nullptr, 0, 0, 0};
+  const uint32_t *crc_tab = g_s.fused.tables(ctype);
+  const uint32_t groups = (flags >> 8) ? (flags >> 8) : g_s.fused.groups;
+  hipStream_t st = stream ? static_cast<hipStream_t>(stream) : g_s.st;
+  auto launches = [&] {
+    hipError_t le = launch_probe(dv, uint32_t(n), proto, chunk_size, ctype, pkts != nullptr, max_pkts, st);
+    if (le == hipSuccess) le = launch_unframe_window_batch(dv, uint32_t(n), uint32_t(proto), crc_tab, groups, st);
+    return le;
+  };
+  hipError_t he = hipMemcpyAsync(dv + T.in, pin + T.in, n * sizeof(Entry), hipMemcpyHostToDevice, st);
+  if (he == hipSuccess) he = launches();
+  if (he == hipSuccess)
+    he = hipMemcpyAsync(pin + T.desc, dv + T.desc, T.bytes - T.desc, hipMemcpyDeviceToHost, st);
+  if (he == hipSuccess && timing) {
+    he = hipEventRecord(g_s.ev[0], st);
+    for (int i = 0; i < iters && he == hipSuccess; i++) he = launches();
+    if (he == hipSuccess) he = hipEventRecord(g_s.ev[1], st);
+  }
+  // always synchronised, even after an error: the tables are out of the device's use before the lock goes
+  const hipError_t se = hipStreamSynchronize(st);
+  if (he == hipSuccess) he = se;
+  if (he != hipSuccess) return fail(HDFS_CRC32C_EHIP, "pread batch: %s", hipGetErrorString(he));
+  if (timing) {
+    float ms = 0;
+    if ((he = hipEventElapsedTime(&ms, g_s.ev[0], g_s.ev[1])) != hipSuccess)
+      return fail(HDFS_CRC32C_EHIP, "pread batch: %s", hipGetErrorString(he));
+    *ms_per_iter = double(ms) / iters;
+  }
+  const Window *desc = reinterpret_cast<const Window *>(pin + T.desc);
+  const uint32_t *slot = reinterpret_cast<const uint32_t *>(pin + T.slot);
+  const uint32_t *status = reinterpret_cast<const uint32_t *>(pin + T.status);
+  const uint32_t nreg = reinterpret_cast<const uint32_t *>(pin + T.meta)[0];
+  int first_neg = 0, first_pos = 0;
+  char neg_text[sizeof(g_err)] = "";
+  for (size_t b = 0; b < n; b++) {
+    hdfs_pread_batch_entry &x = e[b];
+    const uint32_t s = slot[b];
+    if (s != kNoSlot && (s >= nreg || desc[s].d.entry != b))
+      return fail(HDFS_CRC32C_EHIP, "internal: the probe's tables do not add up at entry %zu", b);
+    if (s != kNoSlot && !status[s]) {
+      const Desc &d = desc[s].d;
+      x.rc = 0;
+      x.path = HDFS_PREAD_BATCH_PATH_KERNEL;
+      x.npkts = d.npk;
+      x.consumed = d.consumed;
+      x.delivered = d.delivered;
+      if (pkts)
+        for (uint32_t i = 0; i < d.npk; i++) pkts[b * max_pkts + i] = record_of(packet_of(d, i));
+      continue;
+    }
+    const int r = fallback(x, b, proto, chunk_size, ctype, pkts, max_pkts);
+    if (r < 0 && !first_neg) {
+      first_neg = r;
+      std::memcpy(neg_text, g_err, sizeof(neg_text));
+    }
+    if (r > 0 && !first_pos) first_pos = r;
+  }
+  if (first_neg) {
+    std::memcpy(g_err, neg_text, sizeof(neg_text));
+    return first_neg;
+  }
+  return first_pos;
+}
+
+}  // namespace
+}  // namespace hdfs_pread_batch
+
+using namespace hdfs_pread_batch;
+
+extern "C" {
+
+int hdfs_pread_batch_abi_version(void) { return HDFS_PREAD_BATCH_ABI_VERSION; }
+
+const char *hdfs_pread_batch_last_error(void) { return hdfs_companion::last_error(); }
+
+int hdfs_pread_batch_read(hdfs_pread_batch_entry *e, size_t n, int proto, uint32_t chunk_size, int ctype,
+                          hdfs_crc32c_packet *pkts, size_t max_pkts, void *stream) {
+  return read_windows(e, n, proto, chunk_size, ctype, pkts, max_pkts, stream, false, 0u, 0, nullptr);
+}
+
+int hdfs_pread_batch_time(hdfs_pread_batch_entry *e, size_t n, int proto, uint32_t chunk_size, int ctype,
+                          unsigned flags, int iters, double *ms_per_iter) {
+  return read_windows(e, n, proto, chunk_size, ctype, nullptr, 0, nullptr, true, flags, iters, ms_per_iter);
+}
+
+}  // extern "C"

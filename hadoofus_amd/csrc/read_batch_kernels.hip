@@ -52,12 +52,11 @@
 #include "crc32c_outpkt.h"
 #include "read_batch_internal.h"
 #include "read_batch_layout.h"
+#include "read_batch_verify.h"
 #include "wire_fused_batch_lookup.h"
 #include "wire_fused_round.h"
 
 namespace hdfs_read_batch {
-
-using namespace hdfs_wire_fused;  // the round: Unit, range_of, load_round, store_round, transpose, fold8, crc::
 
 #define CAS __attribute__((address_space(4)))
 
@@ -105,16 +104,6 @@ __global__ __launch_bounds__(1024) void probe_kernel(const Entry *__restrict__ i
 }
 
 // ---- the main launch ------------------------------------------------------------------
-// The wave's round of a packet, and what the comparison needs beside it.
-// u.h0, u.c0, u.d0: the packet's regions in the STREAM; u.src: the round's
-// first byte there; u.dst: in the destination.
-struct Round {
-  Unit u;
-  uintptr_t out0;    // the packet's first byte in the destination
-  uintptr_t status;  // its entry's status word
-  uint32_t sync;     // the header's syncBlock value, when it has one (u.hb above the canonical length)
-};
-
 FUSED_DEV Round round_at(const CAS Desc *tab, const CAS uint32_t *pk0, uintptr_t status, uint32_t nw, uint32_t total,
                          uint32_t g, uint32_t &k, uint32_t wave) {
   const bool in = g < total;
@@ -148,43 +137,6 @@ FUSED_DEV Round round_at(const CAS Desc *tab, const CAS uint32_t *pk0, uintptr_t
   u.dst = r.out0 + uintptr_t(kRound) * wave;
   r.status = status + 4u * uintptr_t(k);
   return r;
-}
-
-FUSED_DEV uint32_t load32(__amdgpu_buffer_rsrc_t r, uint32_t o) {
-  return __builtin_amdgcn_raw_buffer_load_b32(r, o, 0, 0);
-}
-
-// The wire bytes of the round's CRCs: lane 8c loads chunk c's (any byte
-// address; the range is exactly the round's CRC words).
-FUSED_DEV uint32_t load_crcs(const Unit &u, uint32_t wave, uint32_t lane) {
-  const __amdgpu_buffer_rsrc_t r = range_of(u.c0 + 4u * uintptr_t(kRoundChunks * wave), 4u * u.nfr);
-  return load32(r, (lane & 7u) == 0u ? 4u * (lane >> 3) : kNowhere);
-}
-
-// The lane saw something that is not what it expected: 1 into the entry's
-// status word.  Issued by every lane (the others' offset is outside the range).
-FUSED_DEV void flag(const Round &r, bool bad) {
-  store32(range_of(r.status, 4u), bad ? 0u : kNowhere, 1u);
-}
-
-// The CRCs of the round's full chunks, from the registers of its loads,
-// against the stream's: crc_round with the store turned into a comparison.
-FUSED_DEV bool verify_round(const uint32_t *img, const u32x4 (&v)[4], uint32_t wire, const Unit &u, uint32_t lane,
-                            uint32_t init512) {
-  uint32_t val = 0u;
-  if (u.nfr) {  // uniform; no vector-memory access inside
-    uint32_t d[16];
-#pragma unroll
-    for (int k = 0; k < 4; k++) {
-      d[4 * k + 0] = v[k].x;
-      d[4 * k + 1] = v[k].y;
-      d[4 * k + 2] = v[k].z;
-      d[4 * k + 3] = v[k].w;
-    }
-    transpose(d);
-    val = crc::chunk_final(fold8(crc::piece_shift(img, lane & 7u, crc::piece_raw(img, lane, d))), init512);
-  }
-  return (lane & 7u) == 0u && (lane >> 3) < u.nfr && wire != val;
 }
 
 // The packet's header, by one whole wave: lane 0 composes the expected one

@@ -5,8 +5,12 @@ streams of many block transfers verified and de-framed into device buffers by
 one launch) lives in libhadoofus_read_batch.so, built by hadoofus_amd.build
 beside the product library and loaded on first use (read_batch.py).  A thin
 ctypes mirror of that ABI on hadoofus_amd.companion's loader: no compute here
-and no fallback of its own.  Importing the package loads nothing.
+and no fallback of its own.  A batch of positional reads
+(include/hadoofus_pread_batch.h: each read's window of its stream) lives in
+libhadoofus_pread_batch.so, built and loaded the same way (pread_batch.py, the
+module hadoofus_read.pread_batch).  Importing the package loads nothing.
 """
+from . import pread_batch  # noqa: F401  (binds nothing until first use)
 from .read_batch import (  # noqa: F401  (binds nothing until first use)
     ABI_VERSION, LIB_PATH, MAX_ENTRIES, MAX_GROUPS, PATH_FALLBACK, PATH_KERNEL, Entry, entry, read_blocks, time,
     time_groups,

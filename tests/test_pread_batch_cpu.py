@@ -1,0 +1,365 @@
+"""CPU tests of the pread batch library (include/hadoofus_pread_batch.h): its
+build beside the others in a table of its own, its ABI, its bindings
+(hadoofus_read.pread_batch), the rejections its entry points decide without a
+GPU, the kernels' metadata, what it shares with the read batch library, and
+the window arithmetic (pread_batch_layout.h) run on the CPU against a
+brute-force frame_step / read_avail walk (tests/consumer/pread_batch_selftest.cpp,
+built with ASan/UBSan, nothing loaded into Python)."""
+import ctypes
+import os
+import re
+import subprocess
+import sys
+import types
+
+import pytest
+
+from abi_symbols import c_functions as _c_functions, declared as _declared
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+EINVAL = -1
+DECLARED = {"hdfs_pread_batch_abi_version", "hdfs_pread_batch_last_error", "hdfs_pread_batch_read",
+            "hdfs_pread_batch_time"}
+NINE = ["md5crc", "writev", "wire", "wire_batch", "wirev", "wire_fused", "wire_fused_batch", "wirev_fused",
+        "wirev_fused_batch"]
+
+
+def _rocm_include():
+    for d in (os.environ.get("ROCM_PATH"), "/opt/rocm"):
+        if d and os.path.exists(os.path.join(d, "include", "hip", "hip_runtime.h")):
+            return os.path.join(d, "include")
+    return None
+
+
+@pytest.fixture(scope="module")
+def libs():
+    """(release library, pread batch library), built if stale."""
+    from hadoofus_amd import build
+    return build.build(), build.PREAD_BATCH_LIB
+
+
+@pytest.fixture(scope="module")
+def pb(libs):
+    from hadoofus_read import pread_batch
+    pread_batch.load()
+    return pread_batch
+
+
+# ---- the window arithmetic on the CPU --------------------------------------------------------
+def test_pread_batch_selftest(tmp_path):
+    exe = tmp_path / "pread_batch_selftest"
+    subprocess.check_call(["g++", "-std=c++17", "-O1", "-Wall", "-Werror", "-fsanitize=address,undefined",
+                           "-D__HIP_PLATFORM_AMD__", "-I" + _rocm_include(), "-I" + os.path.join(ROOT, "include"),
+                           "-I" + os.path.join(ROOT, "hadoofus_amd", "csrc"),
+                           os.path.join(ROOT, "tests", "consumer", "pread_batch_selftest.cpp"), "-o", str(exe)])
+    p = subprocess.run([str(exe)], capture_output=True, text=True, timeout=300)
+    assert p.returncode == 0, p.stdout + p.stderr
+    assert p.stdout.strip().endswith("0 failures"), p.stdout
+    reg, irr = map(int, re.search(r"(\d+) regular, (\d+) irregular verdicts", p.stdout).groups())
+    assert reg > 10000 and irr > 10000, p.stdout
+
+
+# ---- build -----------------------------------------------------------------------------------
+def test_build_produces_the_library_beside_the_others(libs):
+    lib, plib = libs
+    assert os.path.exists(plib) and os.path.basename(plib) == "libhadoofus_pread_batch.so"
+    assert os.path.dirname(lib) == os.path.dirname(plib)
+    from hadoofus_amd import build
+    assert os.path.exists(build.READ_BATCH_LIB)
+
+
+def test_build_tables():
+    """The nine companions and the read side's table are untouched; positional
+    reads have a table of their own with rows of the same shape."""
+    from hadoofus_amd import build
+    assert [c[0] for c in build.COMPANIONS] == NINE
+    assert [r[0] for r in build.READ_LIBRARIES] == ["read_batch"]
+    assert [r[0] for r in build.PREAD_LIBRARIES] == ["pread_batch"]
+    for stem, sources, headers, public in build.PREAD_LIBRARIES:
+        up = stem.upper()
+        assert build.companion_lib(stem) == getattr(build, up + "_LIB")
+        assert (sources, headers, public) == (getattr(build, up + "_SOURCES"), getattr(build, up + "_HEADERS"),
+                                              getattr(build, up + "_PUBLIC"))
+        assert f"{stem}_exports.map" in headers and f"hadoofus_{stem}.h" in public
+        assert all(os.path.exists(os.path.join(build.CSRC, f)) for f in sources + headers)
+        assert all(os.path.exists(os.path.join(build.INCLUDE, f)) for f in public)
+    assert build.PREAD_BATCH_SOURCES == ["pread_batch_kernels.hip", "pread_batch.cpp"]
+    assert {"pread_batch_internal.h", "pread_batch_layout.h", "read_batch_layout.h", "read_batch_verify.h",
+            "wire_fused_round.h", "wire_fused_batch_lookup.h", "crc32c_frame.h",
+            "companion_support.h"} <= set(build.PREAD_BATCH_HEADERS)
+    assert "read_batch_verify.h" in build.READ_BATCH_HEADERS  # shared: a change rebuilds both
+    assert "libhadoofus_pread_batch.so" in build.__doc__ and "PREAD_LIBRARIES" in build.__doc__
+
+
+def test_sources_share_the_round_and_the_layout_and_copy_none():
+    from hadoofus_amd import build
+    read = lambda f: open(os.path.join(build.CSRC, f)).read()  # noqa: E731
+    code = lambda f: "\n".join(l for l in read(f).splitlines() if not l.lstrip().startswith("//"))  # noqa: E731
+    kern, host, lay, shared = (code(f) for f in ("pread_batch_kernels.hip", "pread_batch.cpp", "pread_batch_layout.h",
+                                                 "read_batch_verify.h"))
+    for inc in ("wire_fused_round.h", "wire_fused_batch_lookup.h", "crc32c_frame.h", "crc32c_outpkt.h",
+                "pread_batch_layout.h", "read_batch_verify.h"):
+        assert f'#include "{inc}"' in kern, inc
+    for inc in ("read_batch_layout.h", "crc32c_frame.h"):
+        assert f'#include "{inc}"' in lay, inc
+    for inc in ("companion_support.h", "wire_fused_host.h", "wire_fused_tables.h", "pread_batch_layout.h"):
+        assert f'#include "{inc}"' in host, inc
+    # the layout header is host and device arithmetic with no HIP runtime call
+    assert "HDFS_HD" in lay and not re.search(r"\bhip[A-Z]\w*\(", lay)
+    for name in ("probe_entry(", "packet_of", "record_of", "prefix_regular"):
+        assert name in lay, name
+    # the comparison helpers live once, in the header both kernel files include
+    rkern = code("read_batch_kernels.hip")
+    assert '#include "read_batch_verify.h"' in rkern
+    for name in ("load_crcs(", "verify_round(", "flag("):
+        assert re.search(r"FUSED_DEV \w+ " + re.escape(name), shared), name
+        for src in (kern, rkern):
+            assert not re.search(r"FUSED_DEV \w+ " + re.escape(name), src), name
+    # nothing of the round or of the lookups is defined again
+    for f in build.PREAD_BATCH_SOURCES + ["pread_batch_internal.h", "pread_batch_layout.h", "read_batch_verify.h"]:
+        src = code(f)
+        for name in ("range_of(", "load16(", "store16(", "store32(", "load8(", "store8(", "fold8(", "transpose(",
+                     "unit_of(", "load_round(", "store_round(", "crc_round(", "ragged_chunk(", "fill_image("):
+            assert not re.search(r"FUSED_DEV [\w:<> ]*\b" + re.escape(name), src), (f, name)
+        for name in ("uint32_t write_of(", "uint32_t frag_of(", "void count_packet(", "bool seek_write(",
+                     "build_layout(", "struct Unit {", "permlane", "atomic", "hdfs_crc32c_plan_"):
+            assert name not in src, (f, name)
+        for poly in ("82f63b78", "edb88320"):
+            assert poly not in src.lower(), (f, poly)
+    for name in ("write_of(pk0, nw, g, k)", "load_round(", "store_round(", "store16(", "store8(", "range_of(",
+                 "address_space(4)", "kNowhere", "probe_window("):
+        assert name in kern, name
+    assert host.count("hdfs_crc32c_read_packets(") >= 1 and host.count("hipMemcpyAsync(") == 2
+    assert "x.client_offset, x.read_len" in host and "READ_ALL, &iov" not in host
+
+
+# ---- ABI -------------------------------------------------------------------------------------
+def test_library_exports_exactly_its_header(libs):
+    _, plib = libs
+    assert _declared("hadoofus_pread_batch.h") == DECLARED
+    funcs = _c_functions(plib)
+    assert set(funcs) == DECLARED, set(funcs) ^ DECLARED
+    txt = open(os.path.join(ROOT, "include", "hadoofus_pread_batch.h")).read()
+    v = int(re.search(r"#define HDFS_PREAD_BATCH_ABI_VERSION (\d+)", txt).group(1))
+    assert v == 1 and set(funcs.values()) == {f"HADOOFUS_PREAD_BATCH_{v}"}, funcs
+
+
+def test_library_links_the_one_engine_through_four_calls(libs):
+    lib, plib = libs
+    dyn = subprocess.check_output(["readelf", "-d", plib], text=True)
+    needed = re.findall(r"\(NEEDED\)\s+Shared library: \[(.*?)\]", dyn)
+    assert [n for n in needed if "hadoofus" in n] == ["libhadoofus_crc32c.so"] and "$ORIGIN" in dyn
+    und = subprocess.check_output(["nm", "-D", "--undefined-only", plib], text=True)
+    engine = sorted(l.split()[-1].split("@")[0] for l in und.splitlines() if "hdfs_" in l)
+    assert engine == ["hdfs_crc32c_bound_device", "hdfs_crc32c_init", "hdfs_crc32c_last_error",
+                      "hdfs_crc32c_read_packets"]
+    main = subprocess.check_output(["nm", "-D", "--defined-only", lib], text=True)
+    assert all(s in main for s in engine) and "hdfs_pread_batch" not in main
+
+
+def test_header_compiles_as_c99(tmp_path):
+    src = tmp_path / "t.c"
+    src.write_text('#include "hadoofus_pread_batch.h"\n'
+                   "typedef char entry_is_80_bytes[sizeof(hdfs_pread_batch_entry) == 80 ? 1 : -1];\n"
+                   "int main(void){ return (int)sizeof(hdfs_pread_batch_entry) - 80 + HDFS_PREAD_BATCH_ABI_VERSION - 1 + "
+                   "(int)HDFS_PREAD_BATCH_TIME_GROUPS(0) + HDFS_PREAD_BATCH_MAX_ENTRIES - 1024 + "
+                   "HDFS_PREAD_BATCH_PATH_KERNEL + HDFS_PREAD_BATCH_PATH_FALLBACK - 1; }\n")
+    subprocess.check_call(["gcc", "-std=c99", "-pedantic", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"),
+                           "-c", str(src), "-o", str(tmp_path / "t.o")])
+
+
+def test_struct_layout_matches_c(tmp_path):
+    from hadoofus_read import pread_batch
+    S = pread_batch.Entry
+    names = [f for f, _ in S._fields_]
+    src = tmp_path / "l.c"
+    src.write_text('#include <stddef.h>\n#include <stdio.h>\n#include "hadoofus_pread_batch.h"\n'
+                   'int main(void){ printf("%zu", sizeof(hdfs_pread_batch_entry));\n' +
+                   "".join(f'printf(" %zu", offsetof(hdfs_pread_batch_entry, {n}));\n' for n in names) +
+                   "return 0; }\n")
+    exe = tmp_path / "l"
+    subprocess.check_call(["gcc", "-std=c99", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), str(src),
+                           "-o", str(exe)])
+    got = [int(x) for x in subprocess.check_output([str(exe)], text=True).split()]
+    assert got == [ctypes.sizeof(S)] + [getattr(S, n).offset for n in names]
+    assert got == [80, 0, 8, 16, 24, 32, 40, 48, 56, 64, 72, 76]  # pinned: the ABI of version 1
+
+
+def test_c_consumer_links(tmp_path, libs):
+    lib, _ = libs
+    libdir = os.path.dirname(lib)
+    exe = tmp_path / "pread_batch_consumer"
+    subprocess.check_call(["gcc", "-std=c99", "-O2", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"),
+                           os.path.join(ROOT, "tests", "consumer", "pread_batch_consumer.c"), "-o", str(exe),
+                           "-L", libdir, "-Wl,-rpath," + libdir, "-lhadoofus_pread_batch", "-lhadoofus_crc32c"])
+    assert exe.exists()
+
+
+# ---- bindings ----------------------------------------------------------------------------------
+def test_import_loads_nothing_and_the_package_keeps_its_names():
+    code = ("import hadoofus_read as r\nfrom hadoofus_amd import abi\nfrom hadoofus_read import pread_batch, read_batch\n"
+            "assert abi._lib is None and read_batch._lib is None and pread_batch._lib is None\n"
+            "assert r.pread_batch is pread_batch and r.read_blocks is read_batch.read_blocks and r.time is read_batch.time\n"
+            "for name in ('ABI_VERSION', 'LIB_PATH', 'MAX_ENTRIES', 'MAX_GROUPS', 'PATH_FALLBACK', 'PATH_KERNEL', 'Entry',\n"
+            "             'entry', 'read_blocks', 'time', 'time_groups'):\n"
+            "    assert getattr(r, name) is getattr(read_batch, name), name\n"
+            "for name in ('LIB_PATH', 'ABI_VERSION', 'MAX_ENTRIES', 'MAX_GROUPS', 'PATH_KERNEL', 'PATH_FALLBACK', 'Entry',\n"
+            "             'entry', 'entries', 'read', 'time', 'time_groups', 'load', 'check_abi', 'bind', '_check'):\n"
+            "    assert hasattr(pread_batch, name), name\n")
+    subprocess.check_call([sys.executable, "-c", code], cwd=ROOT)
+
+
+def test_loading_is_cached_and_a_missing_library_is_refused(libs, pb, tmp_path):
+    from hadoofus_amd import build
+    lib = pb.load()
+    assert lib is not None and pb.load() is lib and pb._lib is lib
+    assert pb.LIB_PATH == build.PREAD_BATCH_LIB and lib.hdfs_pread_batch_abi_version() == pb.ABI_VERSION == 1
+    missing = str(tmp_path / "libhadoofus_pread_batch.so")
+    code = ("from hadoofus_read import pread_batch as m\n"
+            f"path = {missing!r}\n"
+            "try:\n"
+            "    m.load(path=path)\n"
+            "except ImportError as e:\n"
+            "    assert path in str(e) and 'hadoofus_amd.build' in str(e), e\n"
+            "else:\n"
+            "    raise SystemExit('a library that is not there was loaded')\n"
+            "assert m._lib is None\n"
+            "assert m.load() is m._lib is not None\n")
+    subprocess.check_call([sys.executable, "-c", code], cwd=ROOT)
+
+
+def test_a_wrong_abi_is_refused():
+    from hadoofus_read import pread_batch as m
+    other = types.SimpleNamespace(hdfs_pread_batch_abi_version=lambda: 2)
+    with pytest.raises(ImportError) as e:
+        m.check_abi(other)
+    assert "pread batch library ABI version 2, bindings written for 1" in str(e.value)
+    same = types.SimpleNamespace(hdfs_pread_batch_abi_version=lambda: 1)
+    assert m.check_abi(same) is same
+
+
+def test_entry_helper():
+    from hadoofus_read import pread_batch as m
+
+    class T:  # what companion.ptr takes of a torch tensor
+        def __init__(self, p, n):
+            self.p, self.n = p, n
+
+        def data_ptr(self):
+            return self.p
+
+        def numel(self):
+            return self.n
+
+        def element_size(self):
+            return 1
+    assert m.entry(0x1000, 10, 0x2000, 20, 700, 5) == dict(stream_ptr=0x1000, nbytes=10, dst_ptr=0x2000, dst_cap=20,
+                                                          client_offset=700, read_len=5)
+    assert m.entry(T(0x1000, 10), None, T(0x2000, 20), client_offset=3, read_len=4) == \
+        dict(stream_ptr=0x1000, nbytes=10, dst_ptr=0x2000, dst_cap=20, client_offset=3, read_len=4)
+    arr = m.entries([m.entry(0x1000, 10, 0x2000, 20, 1 << 40, 7)] * 2)
+    assert (arr[1].stream, arr[1].len, arr[1].dst, arr[1].dst_cap, arr[1].client_offset, arr[1].read_len) == \
+        (0x1000, 10, 0x2000, 20, 1 << 40, 7)
+    assert m.time_groups(3) == 3 << 8 and m.MAX_GROUPS == 1024 and m.MAX_ENTRIES == 1024
+
+
+# ---- rejections that need no device ---------------------------------------------------------------
+def test_rejections_without_a_device(pb):
+    from hadoofus_amd.abi import Packet
+    lib = pb.load()
+    pk = (Packet * 8)()
+    before = bytes(pk)
+    # never dereferenced: every call is decided by its arguments
+    good = [pb.entry(0x1000, 1000, 0x100000, 1000, 512, 100)] * 3
+
+    def call(batch=good, n=None, proto=2, cs=512, ctype=2, arr=None):
+        arr = pb.entries(batch) if arr is None else arr
+        for e in arr:
+            e.rc, e.path, e.npkts, e.consumed, e.delivered = 7, 7, 7, 7, 7
+        rc = lib.hdfs_pread_batch_read(arr, len(batch) if n is None else n, proto, cs, ctype, pk, 2, None)
+        return rc, arr, lib.hdfs_pread_batch_last_error().decode()
+    zeros = [(0, 0, 0, 0, pb.PATH_FALLBACK)] * 3
+    outs = lambda arr: [(e.rc, e.npkts, e.consumed, e.delivered, e.path) for e in arr]  # noqa: E731
+    for kw, text in ((dict(proto=0), "proto"), (dict(proto=3), "proto"), (dict(ctype=3), "checksum type"),
+                     (dict(ctype=-1), "checksum type"), (dict(ctype=0), "CRC32 or CRC32C"),
+                     (dict(cs=0), "chunk_size")):
+        rc, arr, err = call(**kw)
+        assert rc == EINVAL and "entry 0" in err and text in err and b"device" not in err.encode(), (kw, err)
+        assert outs(arr) == zeros
+    for rl, text in ((0, "read_len 0"), (-5, "read_len -5"), (-1, "hdfs_read_batch_read_blocks")):
+        rc, arr, err = call([good[0], pb.entry(0x1000, 1000, 0x100000, 1000, 512, rl), good[0]])
+        assert rc == EINVAL and "entry 1" in err and text in err and b"device" not in err.encode(), (rl, err)
+        assert outs(arr) == zeros
+    rc, _, err = call(n=0)
+    assert rc == EINVAL and "no entries" in err
+    rc, _, err = call(n=pb.MAX_ENTRIES + 1, arr=(pb.Entry * (pb.MAX_ENTRIES + 1))())
+    assert rc == EINVAL and "1025 entries" in err and "1024" in err
+    assert lib.hdfs_pread_batch_read(None, 3, 2, 512, 2, pk, 2, None) == EINVAL
+    rc, _, err = call([good[0], pb.entry(None, 5, 0x2000, 5, 0, 1)])
+    assert rc == EINVAL and "entry 1" in err and "stream" in err
+    rc, _, err = call([good[0], good[0], pb.entry(0x1000, 5, None, 5, 0, 1)])
+    assert rc == EINVAL and "entry 2" in err and "destination" in err
+    assert bytes(pk) == before
+    with pytest.raises(pb.abi.CRC32CError) as e:  # through the bindings: the call's own refusal raises
+        pb.read(good, proto=7)
+    assert e.value.code == EINVAL and "proto" in str(e.value)
+
+
+def test_timing_argument_errors(pb):
+    lib, ms = pb.load(), ctypes.c_double(5)
+    one = [pb.entry(0x1000, 100, 0x2000, 100, 0, 50)]
+
+    def call(flags=0, iters=1, out=ctypes.byref(ms), proto=2):
+        arr = pb.entries(one)
+        rc = lib.hdfs_pread_batch_time(arr, 1, proto, 512, 2, flags, iters, out)
+        assert (arr[0].rc, arr[0].npkts, arr[0].consumed, arr[0].delivered) == (0, 0, 0, 0)
+        return rc, lib.hdfs_pread_batch_last_error()
+    # every one decided before a device is asked (0x1000 is no device memory: going on would say so)
+    for kw in (dict(iters=0), dict(iters=-3), dict(out=None)):
+        rc, err = call(**kw)
+        assert rc == EINVAL and b"iters" in err and b"device" not in err, (kw, err)
+    assert call(proto=7)[0] == EINVAL
+    for flags in (pb.time_groups(pb.MAX_GROUPS + 1), pb.time_groups(1 << 23), 1, pb.time_groups(2) | 4):
+        rc, err = call(flags=flags)
+        assert rc == EINVAL and b"workgroups" in err, (flags, err)
+    assert ms.value == 0  # set to 0 by every call that was given it
+
+
+def test_last_error_text_is_its_own(pb):
+    from hadoofus_read import read_batch as rb
+    rl, lib = rb.load(), pb.load()
+    assert rl.hdfs_read_batch_read_blocks(rb.entries([rb.entry(0x1000, 5, 0x2000, 5)]), 1, 7, 512, 2, None, 0,
+                                          None) == EINVAL
+    before = rl.hdfs_read_batch_last_error()
+    assert lib.hdfs_pread_batch_read(pb.entries([pb.entry(0x1000, 5, 0x2000, 5, 0, 1)]), 1, 2, 0, 2, None, 0,
+                                     None) == EINVAL
+    assert lib.hdfs_pread_batch_last_error() == b"entry 0: chunk_size 0"
+    assert rl.hdfs_read_batch_last_error() == before and b"proto" in before
+
+
+# ---- the kernels' metadata --------------------------------------------------------------------------
+def test_kernel_metadata(tmp_path):
+    """hipcc -S of the kernel file: neither kernel has a private segment (no
+    scratch), the main kernel's LDS is all dynamic (the table image and the
+    expected header) and its registers leave room for 16 waves a workgroup
+    (1024 threads are four waves a SIMD: at most 128 VGPRs), the probe's LDS is
+    its two count arrays."""
+    from hadoofus_amd import build
+    asm = tmp_path / "pread_batch_kernels.s"
+    subprocess.check_call([build._hipcc(), f"--offload-arch={build.ARCH}", "-O3", "-std=c++17", "--cuda-device-only",
+                           "-S", f"-I{build.INCLUDE}", f"-I{build.CSRC}",
+                           os.path.join(build.CSRC, "pread_batch_kernels.hip"), "-o", str(asm)])
+    txt = asm.read_text()
+    meta = {}
+    for block in txt.split("  - .agpr_count:")[1:]:
+        name = re.search(r"\.name:\s+(\S+)", block).group(1)
+        meta[name] = {k: int(v) for k, v in re.findall(
+            r"\.(vgpr_count|sgpr_count|private_segment_fixed_size|group_segment_fixed_size|vgpr_spill_count|"
+            r"max_flat_workgroup_size):\s+(\d+)", block)}
+    probe = next(v for k, v in meta.items() if "pread_probe_kernel" in k)
+    main = next(v for k, v in meta.items() if "unframe_window_batch_kernel" in k)
+    assert len(meta) == 2
+    for k in (probe, main):
+        assert k["private_segment_fixed_size"] == 0 and k["vgpr_spill_count"] == 0
+        assert k["max_flat_workgroup_size"] == 1024 and k["vgpr_count"] <= 128
+    assert main["group_segment_fixed_size"] == 0 and probe["group_segment_fixed_size"] == 8192
