@@ -67,6 +67,18 @@ builds on read_batch_layout.h), shares the round's comparisons with the read
 batch library (read_batch_verify.h, compiled into both) and hands what it does
 not take to hdfs_crc32c_read_packets with the entry's window.  Its bindings
 are hadoofus_read/pread_batch.py.
+
+Scatter reads have a fourth table, PREADV_LIBRARIES, rows of that shape again:
+libhadoofus_preadv_batch.so (include/hadoofus_preadv_batch.h) is built with the
+others, the same way, from its own sources and export map.  It runs the pread
+batch's round with a scatter store over a list of device fragments per read:
+the window arithmetic of pread_batch_layout.h, the comparisons of
+read_batch_verify.h and read_batch_header.h, both lookups
+(wire_fused_batch_lookup.h, wirev_fused_lookup.h) and the piece walk of
+preadv_batch_lookup.h, and hands what it does not take to
+hdfs_crc32c_read_packets with the entry's window and fragment list.  Its
+bindings are hadoofus_read/preadv_batch.py.  No source of the pread batch
+library changes for it.
 """
 import os
 import subprocess
@@ -177,6 +189,19 @@ PREAD_BATCH_PUBLIC = ["hadoofus_pread_batch.h", "hadoofus_crc32c.h"]
 PREAD_LIBRARIES = (
     ("pread_batch", PREAD_BATCH_SOURCES, PREAD_BATCH_HEADERS, PREAD_BATCH_PUBLIC),
 )
+PREADV_BATCH_LIB = companion_lib("preadv_batch")
+PREADV_BATCH_SOURCES = ["preadv_batch_kernels.hip", "preadv_batch.cpp"]
+PREADV_BATCH_HEADERS = ["preadv_batch_internal.h", "preadv_batch_lookup.h", "read_batch_header.h",
+                        "pread_batch_internal.h", "pread_batch_layout.h", "read_batch_layout.h", "read_batch_verify.h",
+                        "wirev_fused_internal.h", "wirev_fused_lookup.h", "wire_fused_batch_lookup.h",
+                        "wire_fused_round.h", "wire_fused_crc.h", "wire_fused_tables.h", "wire_fused_host.h",
+                        "wire_internal.h", "crc32c_frame.h", "crc32c_outpkt.h", "crc32c_tables.h",
+                        "companion_support.h", "preadv_batch_exports.map"]
+PREADV_BATCH_PUBLIC = ["hadoofus_preadv_batch.h", "hadoofus_crc32c.h"]
+# The scatter-read libraries, rows as in COMPANIONS; their bindings are hadoofus_read/<stem>.py.
+PREADV_LIBRARIES = (
+    ("preadv_batch", PREADV_BATCH_SOURCES, PREADV_BATCH_HEADERS, PREADV_BATCH_PUBLIC),
+)
 ARCH = os.environ.get("HADOOFUS_OFFLOAD_ARCH", "gfx950")
 
 
@@ -218,8 +243,8 @@ def build(force=False, verbose=False, diag=True):
     """Build the release library (and, with diag=True, the diagnostic one,
     in parallel), then the MD5CRC, gather-write, wire-stream, wire-batch,
     gather-wire, fused-wire, fused-wire-batch, fused-gather-wire and
-    fused-gather-wire-batch companions, the read side's libraries and the
-    positional-read libraries (in parallel).
+    fused-gather-wire-batch companions, the read side's libraries, the
+    positional-read libraries and the scatter-read libraries (in parallel).
     Returns the release library's path."""
     os.makedirs(LIBDIR, exist_ok=True)
     jobs = []
@@ -238,7 +263,7 @@ def build(force=False, verbose=False, diag=True):
         os.replace(out + ".tmp", out)
     # the companions link against the release library, so after it is in place
     procs = []
-    for stem, sources, headers, public in COMPANIONS + READ_LIBRARIES + PREAD_LIBRARIES:
+    for stem, sources, headers, public in COMPANIONS + READ_LIBRARIES + PREAD_LIBRARIES + PREADV_LIBRARIES:
         out = companion_lib(stem)
         if force or _stale(out, sources, headers, public, [LIB]):
             cmd = _companion_cmd(out + ".tmp", sources, f"{stem}_exports.map")

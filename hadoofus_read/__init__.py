@@ -8,9 +8,14 @@ ctypes mirror of that ABI on hadoofus_amd.companion's loader: no compute here
 and no fallback of its own.  A batch of positional reads
 (include/hadoofus_pread_batch.h: each read's window of its stream) lives in
 libhadoofus_pread_batch.so, built and loaded the same way (pread_batch.py, the
-module hadoofus_read.pread_batch).  Importing the package loads nothing.
+module hadoofus_read.pread_batch).  A batch of scatter reads
+(include/hadoofus_preadv_batch.h: each read's window laid over a list of device
+fragments) lives in libhadoofus_preadv_batch.so, built and loaded the same way
+(preadv_batch.py, the module hadoofus_read.preadv_batch).  Importing the
+package loads nothing.
 """
 from . import pread_batch  # noqa: F401  (binds nothing until first use)
+from . import preadv_batch  # noqa: F401  (binds nothing until first use)
 from .read_batch import (  # noqa: F401  (binds nothing until first use)
     ABI_VERSION, LIB_PATH, MAX_ENTRIES, MAX_GROUPS, PATH_FALLBACK, PATH_KERNEL, Entry, entry, read_blocks, time,
     time_groups,
