@@ -79,6 +79,18 @@ preadv_batch_lookup.h, and hands what it does not take to
 hdfs_crc32c_read_packets with the entry's window and fragment list.  Its
 bindings are hadoofus_read/preadv_batch.py.  No source of the pread batch
 library changes for it.
+
+Checksums taken from packet streams have a fifth table, DIGEST_LIBRARIES, rows
+of that shape once more: libhadoofus_md5crc_streams.so
+(include/hadoofus_md5crc_streams.h) is built with the others, the same way,
+from its own sources and export map.  It digests the chunk CRCs where the fused
+write libraries and the read batch libraries leave them, inside the wire
+streams: the read batch's probe arithmetic (read_batch_layout.h) and header
+comparison (read_batch_header.h, read_batch_verify.h), the MD5 rounds of
+md5_core.h and the cursor of md5crc_streams_lookup.h over the packets' CRC
+regions, and hands what is not of the regular shape to
+hdfs_crc32c_parse_packets.  It links neither the MD5CRC library nor any other
+companion.  Its bindings are hadoofus_read/md5crc_streams.py.
 """
 import os
 import subprocess
@@ -202,6 +214,17 @@ PREADV_BATCH_PUBLIC = ["hadoofus_preadv_batch.h", "hadoofus_crc32c.h"]
 PREADV_LIBRARIES = (
     ("preadv_batch", PREADV_BATCH_SOURCES, PREADV_BATCH_HEADERS, PREADV_BATCH_PUBLIC),
 )
+MD5CRC_STREAMS_LIB = companion_lib("md5crc_streams")
+MD5CRC_STREAMS_SOURCES = ["md5crc_streams_kernels.hip", "md5crc_streams.cpp"]
+MD5CRC_STREAMS_HEADERS = ["md5crc_streams_internal.h", "md5crc_streams_lookup.h", "md5_core.h", "read_batch_layout.h",
+                          "read_batch_header.h", "read_batch_verify.h", "wire_fused_batch_lookup.h",
+                          "wire_fused_round.h", "wire_fused_crc.h", "wire_internal.h", "crc32c_frame.h",
+                          "crc32c_outpkt.h", "companion_support.h", "md5crc_streams_exports.map"]
+MD5CRC_STREAMS_PUBLIC = ["hadoofus_md5crc_streams.h", "hadoofus_md5crc.h", "hadoofus_crc32c.h"]
+# The libraries that digest packet streams, rows as in COMPANIONS; their bindings are hadoofus_read/<stem>.py.
+DIGEST_LIBRARIES = (
+    ("md5crc_streams", MD5CRC_STREAMS_SOURCES, MD5CRC_STREAMS_HEADERS, MD5CRC_STREAMS_PUBLIC),
+)
 ARCH = os.environ.get("HADOOFUS_OFFLOAD_ARCH", "gfx950")
 
 
@@ -244,7 +267,8 @@ def build(force=False, verbose=False, diag=True):
     in parallel), then the MD5CRC, gather-write, wire-stream, wire-batch,
     gather-wire, fused-wire, fused-wire-batch, fused-gather-wire and
     fused-gather-wire-batch companions, the read side's libraries, the
-    positional-read libraries and the scatter-read libraries (in parallel).
+    positional-read libraries, the scatter-read libraries and the libraries
+    that digest packet streams (in parallel).
     Returns the release library's path."""
     os.makedirs(LIBDIR, exist_ok=True)
     jobs = []
@@ -263,7 +287,7 @@ def build(force=False, verbose=False, diag=True):
         os.replace(out + ".tmp", out)
     # the companions link against the release library, so after it is in place
     procs = []
-    for stem, sources, headers, public in COMPANIONS + READ_LIBRARIES + PREAD_LIBRARIES + PREADV_LIBRARIES:
+    for stem, sources, headers, public in COMPANIONS + READ_LIBRARIES + PREAD_LIBRARIES + PREADV_LIBRARIES + DIGEST_LIBRARIES:
         out = companion_lib(stem)
         if force or _stale(out, sources, headers, public, [LIB]):
             cmd = _companion_cmd(out + ".tmp", sources, f"{stem}_exports.map")

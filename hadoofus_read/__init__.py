@@ -11,9 +11,14 @@ libhadoofus_pread_batch.so, built and loaded the same way (pread_batch.py, the
 module hadoofus_read.pread_batch).  A batch of scatter reads
 (include/hadoofus_preadv_batch.h: each read's window laid over a list of device
 fragments) lives in libhadoofus_preadv_batch.so, built and loaded the same way
-(preadv_batch.py, the module hadoofus_read.preadv_batch).  Importing the
-package loads nothing.
+(preadv_batch.py, the module hadoofus_read.preadv_batch).  The MD5CRC block
+digests and the file checksum taken from packet streams
+(include/hadoofus_md5crc_streams.h: the chunk CRCs digested where they lie in
+the streams) live in libhadoofus_md5crc_streams.so, built and loaded the same
+way (md5crc_streams.py, the module hadoofus_read.md5crc_streams).  Importing
+the package loads nothing.
 """
+from . import md5crc_streams  # noqa: F401  (binds nothing until first use)
 from . import pread_batch  # noqa: F401  (binds nothing until first use)
 from . import preadv_batch  # noqa: F401  (binds nothing until first use)
 from .read_batch import (  # noqa: F401  (binds nothing until first use)

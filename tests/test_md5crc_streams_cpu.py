@@ -1,0 +1,393 @@
+"""CPU tests of the MD5CRC streams library (include/hadoofus_md5crc_streams.h):
+its build beside the others, its ABI, its bindings
+(hadoofus_read/md5crc_streams.py), the rejections its entry points decide
+without a GPU, the kernels' metadata, and the cursor over the packets' CRC
+regions (md5crc_streams_lookup.h) run on the CPU against a brute-force
+frame_step walk and a plain MD5 (tests/consumer/md5crc_streams_selftest.cpp,
+built with ASan/UBSan, nothing loaded into Python)."""
+import ctypes
+import os
+import re
+import subprocess
+import sys
+import types
+
+import pytest
+
+from abi_symbols import c_functions as _c_functions, declared as _declared
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+EINVAL = -1
+DECLARED = {"hdfs_md5crc_streams_abi_version", "hdfs_md5crc_streams_last_error",
+            "hdfs_md5crc_streams_block_digests", "hdfs_md5crc_streams_file_checksum", "hdfs_md5crc_streams_time"}
+OWN = ["md5crc_streams_kernels.hip", "md5crc_streams.cpp", "md5crc_streams_internal.h", "md5crc_streams_lookup.h"]
+SHARED = ["md5_core.h", "read_batch_layout.h", "read_batch_header.h", "read_batch_verify.h",
+          "wire_fused_batch_lookup.h", "wire_fused_round.h", "crc32c_frame.h", "crc32c_outpkt.h",
+          "companion_support.h"]
+
+
+def _rocm_include():
+    for d in (os.environ.get("ROCM_PATH"), "/opt/rocm"):
+        if d and os.path.exists(os.path.join(d, "include", "hip", "hip_runtime.h")):
+            return os.path.join(d, "include")
+    return None
+
+
+@pytest.fixture(scope="module")
+def libs():
+    """(release library, MD5CRC streams library), built if stale."""
+    from hadoofus_amd import build
+    return build.build(), build.MD5CRC_STREAMS_LIB
+
+
+@pytest.fixture(scope="module")
+def ms(libs):
+    from hadoofus_read import md5crc_streams
+    md5crc_streams.load()
+    return md5crc_streams
+
+
+# ---- the cursor and the digest on the CPU -----------------------------------------------------
+def test_md5crc_streams_selftest(tmp_path):
+    exe = tmp_path / "md5crc_streams_selftest"
+    subprocess.check_call(["g++", "-std=c++17", "-O1", "-Wall", "-Werror", "-fsanitize=address,undefined",
+                           "-D__HIP_PLATFORM_AMD__", "-I" + _rocm_include(), "-I" + os.path.join(ROOT, "include"),
+                           "-I" + os.path.join(ROOT, "hadoofus_amd", "csrc"),
+                           os.path.join(ROOT, "tests", "consumer", "md5crc_streams_selftest.cpp"), "-o", str(exe)])
+    p = subprocess.run([str(exe)], capture_output=True, text=True, timeout=300)
+    assert p.returncode == 0, p.stdout + p.stderr
+    assert p.stdout.strip().endswith("0 failures"), p.stdout
+
+
+def test_the_lookup_header_compiles_without_hip(tmp_path):
+    """Plain C++ with no include path but the header's own directory: integer
+    arithmetic only, as the other lookup headers."""
+    src = tmp_path / "l.cpp"
+    src.write_text('#include "md5crc_streams_lookup.h"\n'
+                   "using namespace hdfs_md5crc_streams;\n"
+                   "int main() { Regions r = Regions{}; r.ntail = 1; r.tail_words0 = 20; r.nwords = count_words(r);\n"
+                   "  Cursor c = start(r); settle(r, c); const bool s = span_ahead(c); take_span(c);\n"
+                   "  return (s && take_word(r, c) == 64 && r.nwords == 20 && join(0x44332211u, 0x88776655u, 1) == "
+                   "0x55443322u) ? 0 : 1; }\n")
+    exe = tmp_path / "l"
+    subprocess.check_call(["g++", "-std=c++17", "-Wall", "-Werror", "-I" + os.path.join(ROOT, "hadoofus_amd", "csrc"),
+                           str(src), "-o", str(exe)])
+    assert subprocess.run([str(exe)]).returncode == 0
+    txt = open(os.path.join(ROOT, "hadoofus_amd", "csrc", "md5crc_streams_lookup.h")).read()
+    assert re.findall(r"#include\s+(\S+)", txt) == ["<stdint.h>"]
+
+
+# ---- build ---------------------------------------------------------------------------------
+def test_build_produces_the_library_beside_the_others(libs):
+    lib, slib = libs
+    assert os.path.exists(slib) and os.path.basename(slib) == "libhadoofus_md5crc_streams.so"
+    assert os.path.dirname(lib) == os.path.dirname(slib)
+
+
+def test_build_tables():
+    """The other tables are untouched; this library has a table of its own with
+    rows of the same shape."""
+    from hadoofus_amd import build
+    assert len(build.COMPANIONS) == 9
+    assert [r[0] for r in build.READ_LIBRARIES + build.PREAD_LIBRARIES + build.PREADV_LIBRARIES] == \
+        ["read_batch", "pread_batch", "preadv_batch"]
+    assert [r[0] for r in build.DIGEST_LIBRARIES] == ["md5crc_streams"]
+    for stem, sources, headers, public in build.DIGEST_LIBRARIES:
+        up = stem.upper()
+        assert build.companion_lib(stem) == getattr(build, up + "_LIB")
+        assert (sources, headers, public) == (getattr(build, up + "_SOURCES"), getattr(build, up + "_HEADERS"),
+                                              getattr(build, up + "_PUBLIC"))
+        assert f"{stem}_exports.map" in headers and f"hadoofus_{stem}.h" in public
+        assert all(os.path.exists(os.path.join(build.CSRC, f)) for f in sources + headers)
+        assert all(os.path.exists(os.path.join(build.INCLUDE, f)) for f in public)
+    assert build.MD5CRC_STREAMS_SOURCES == ["md5crc_streams_kernels.hip", "md5crc_streams.cpp"]
+    assert {"md5crc_streams_internal.h", "md5crc_streams_lookup.h", *SHARED} <= set(build.MD5CRC_STREAMS_HEADERS)
+    assert "hadoofus_md5crc.h" in build.MD5CRC_STREAMS_PUBLIC
+    assert "libhadoofus_md5crc_streams.so" in build.__doc__ and "DIGEST_LIBRARIES" in build.__doc__
+
+
+def test_sources_include_the_shared_code_and_copy_none():
+    from hadoofus_amd import build
+    read = lambda f: open(os.path.join(build.CSRC, f)).read()  # noqa: E731
+    code = lambda f: "\n".join(l for l in read(f).splitlines() if not l.lstrip().startswith("//"))  # noqa: E731
+    kern, host, look = code(OWN[0]), code(OWN[1]), code(OWN[3])
+    for inc in ("md5_core.h", "md5crc_streams_lookup.h", "read_batch_layout.h", "read_batch_header.h",
+                "read_batch_verify.h", "wire_fused_batch_lookup.h", "crc32c_outpkt.h"):
+        assert f'#include "{inc}"' in kern, inc
+    for inc in ("companion_support.h", "hadoofus_md5crc_streams.h", "md5_core.h", "read_batch_layout.h"):
+        assert f'#include "{inc}"' in host, inc
+    every = "".join(read(f) for f in sorted(os.listdir(build.CSRC)))
+    for name in ("uint32_t write_of(", "uint32_t frag_of(", "void count_packet(", "bool seek_write("):
+        assert every.count(name) == 1, name
+    for f in OWN:
+        src = code(f)
+        # no framing arithmetic, no header composition, no comparison and no MD5 round of its own
+        for name in ("probe_entry(At", "frame_step(const", "put_out_header(uint8_t", "put_header_proto(uint8_t",
+                     "HDFS_MD5_STEP", "md5_rotl(", "struct Unit {", "permlane", "atomic", "hdfs_crc32c_plan_",
+                     "__builtin_amdgcn_raw_buffer", "hadoofus_md5crc_internal", "md5crc_internal.h"):
+            assert name not in src, (f, name)
+        for name in ("range_of(", "load8(", "store32(", "verify_header(", "flag(", "md5_block(", "md5_init("):
+            assert not re.search(r"(FUSED_DEV|HDFS_MD5_HD|inline) [\w:<> ]*\b" + re.escape(name), src), (f, name)
+        for poly in ("82f63b78", "edb88320"):
+            assert poly not in src.lower(), (f, poly)
+    for name in ("probe_entry(", "prefix_regular(", "write_of(pk0, nw, g, k)", "verify_header(expect[wave], proto",
+                 "hdfs_read_batch::flag(", "md5_block(st, m)", "block_words(r, c,", "address_space(4)",
+                 "address_space(1)"):
+        assert name in kern, name
+    # the probe has no destination and wants no records
+    assert "~uint64_t(0), proto, chunk_size, ctype, false," in kern
+    # the cursor is the header's; the kernel file only loads
+    for name in ("take_span(", "take_word(", "settle(", "next_region("):
+        assert re.search(r"HDFS_MD5CRC_STREAMS_HD \w+ " + re.escape(name), look), name
+        assert not re.search(r"\w+ " + re.escape(name) + r"[^;]*\{", kern), name
+    assert "hip" not in look.lower().replace("__hipcc__", "").replace("__hip_device_compile__", "")
+    assert host.count("hdfs_crc32c_parse_packets(") == 1 and "hdfs_crc32c_read_packets" not in host
+    assert "hdfs_md5crc_block_digests" not in host and "hdfs_md5crc_file_from_blocks" not in host
+
+
+# ---- ABI -------------------------------------------------------------------------------------
+def test_library_exports_exactly_its_header(libs):
+    _, slib = libs
+    assert _declared("hadoofus_md5crc_streams.h") == DECLARED
+    funcs = _c_functions(slib)
+    assert set(funcs) == DECLARED, set(funcs) ^ DECLARED
+    txt = open(os.path.join(ROOT, "include", "hadoofus_md5crc_streams.h")).read()
+    v = int(re.search(r"#define HDFS_MD5CRC_STREAMS_ABI_VERSION (\d+)", txt).group(1))
+    assert set(funcs.values()) == {f"HADOOFUS_MD5CRC_STREAMS_{v}"}, funcs
+    m = open(os.path.join(ROOT, "hadoofus_amd", "csrc", "md5crc_streams_exports.map")).read()
+    assert "HADOOFUS_MD5CRC_STREAMS_1 {" in m and "hdfs_md5crc_streams_*;" in m
+
+
+def test_library_links_the_one_engine_and_no_companion(libs):
+    lib, slib = libs
+    dyn = subprocess.check_output(["readelf", "-d", slib], text=True)
+    needed = re.findall(r"\(NEEDED\)\s+Shared library: \[(.*?)\]", dyn)
+    assert [n for n in needed if "hadoofus" in n] == ["libhadoofus_crc32c.so"] and "$ORIGIN" in dyn
+    und = subprocess.check_output(["nm", "-D", "--undefined-only", slib], text=True)
+    engine = sorted(l.split()[-1].split("@")[0] for l in und.splitlines() if "hdfs_" in l)
+    assert engine == ["hdfs_crc32c_bound_device", "hdfs_crc32c_init", "hdfs_crc32c_last_error",
+                      "hdfs_crc32c_parse_packets"]
+    main = subprocess.check_output(["nm", "-D", "--defined-only", lib], text=True)
+    assert all(s in main for s in engine) and "hdfs_md5crc_streams" not in main
+
+
+def test_header_says_what_is_not_verified():
+    txt = open(os.path.join(ROOT, "include", "hadoofus_md5crc_streams.h")).read()
+    assert "THE CRCS ARE NOT VERIFIED HERE" in txt and "offset_in_block == 0" in txt and "WHEN IT PAYS" in txt
+    assert '#include "hadoofus_md5crc.h"' in txt and "struct hdfs_md5crc_file_checksum" not in txt
+
+
+def test_header_compiles_as_c99(tmp_path):
+    src = tmp_path / "t.c"
+    src.write_text('#include "hadoofus_md5crc_streams.h"\n'
+                   "int main(void){ return (int)sizeof(hdfs_md5crc_streams_entry) - 80 + "
+                   "HDFS_MD5CRC_STREAMS_ABI_VERSION - 1 + (int)HDFS_MD5CRC_STREAMS_TIME_NONE + "
+                   "HDFS_MD5CRC_STREAMS_MAX_ENTRIES - 1024 + HDFS_MD5CRC_STREAMS_PATH_KERNEL + "
+                   "HDFS_MD5CRC_STREAMS_PATH_FALLBACK - 1 + (int)sizeof(hdfs_md5crc_file_checksum) - 32; }\n")
+    subprocess.check_call(["gcc", "-std=c99", "-pedantic", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"),
+                           "-c", str(src), "-o", str(tmp_path / "t.o")])
+
+
+def test_struct_layout_matches_c(tmp_path):
+    from hadoofus_read import md5crc_streams
+    for S, cname, pinned in ((md5crc_streams.Entry, "hdfs_md5crc_streams_entry",
+                              [80, 0, 8, 16, 24, 32, 40, 48, 56, 60, 64]),  # pinned: the ABI of version 1
+                             (md5crc_streams.FileChecksum, "hdfs_md5crc_file_checksum", [32, 0, 4, 8, 16])):
+        names = [f for f, _ in S._fields_]
+        src = tmp_path / "l.c"
+        src.write_text('#include <stddef.h>\n#include <stdio.h>\n#include "hadoofus_md5crc_streams.h"\n'
+                       f'int main(void){{ printf("%zu", sizeof({cname}));\n' +
+                       "".join(f'printf(" %zu", offsetof({cname}, {n}));\n' for n in names) +
+                       "return 0; }\n")
+        exe = tmp_path / "l"
+        subprocess.check_call(["gcc", "-std=c99", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), str(src),
+                               "-o", str(exe)])
+        got = [int(x) for x in subprocess.check_output([str(exe)], text=True).split()]
+        assert got == [ctypes.sizeof(S)] + [getattr(S, n).offset for n in names]
+        assert got == pinned
+    assert [f for f, _ in md5crc_streams.Entry._fields_] == \
+        ["stream", "len", "consumed", "payload", "nchunks", "npkts", "offset_in_block", "rc", "path", "md5"]
+
+
+def test_c_consumer_links(tmp_path, libs):
+    lib, _ = libs
+    libdir = os.path.dirname(lib)
+    exe = tmp_path / "md5crc_streams_consumer"
+    subprocess.check_call(["gcc", "-std=c99", "-O2", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"),
+                           os.path.join(ROOT, "tests", "consumer", "md5crc_streams_consumer.c"), "-o", str(exe),
+                           "-L", libdir, "-Wl,-rpath," + libdir, "-lhadoofus_md5crc_streams", "-lhadoofus_crc32c"])
+    assert exe.exists()
+
+
+# ---- bindings ----------------------------------------------------------------------------------
+def test_import_loads_nothing():
+    code = ("import hadoofus_read as r\nfrom hadoofus_amd import abi\nfrom hadoofus_read import md5crc_streams as m\n"
+            "assert abi._lib is None and m._lib is None and r.md5crc_streams is m\n"
+            "assert callable(m.block_digests) and callable(m.file_checksum) and callable(m.time) and callable(m.entry)\n"
+            "for name in ('LIB_PATH', 'ABI_VERSION', 'load', 'check_abi', 'bind', '_check'):\n"
+            "    assert hasattr(m, name), name\n")
+    subprocess.check_call([sys.executable, "-c", code], cwd=ROOT)
+
+
+def test_loading_is_cached_and_a_missing_library_is_refused(libs, ms, tmp_path):
+    from hadoofus_amd import build
+    lib = ms.load()
+    assert lib is not None and ms.load() is lib and ms._lib is lib
+    assert ms.LIB_PATH == build.MD5CRC_STREAMS_LIB and lib.hdfs_md5crc_streams_abi_version() == ms.ABI_VERSION == 1
+    missing = str(tmp_path / "libhadoofus_md5crc_streams.so")
+    code = ("from hadoofus_read import md5crc_streams as m\n"
+            f"path = {missing!r}\n"
+            "try:\n"
+            "    m.load(path=path)\n"
+            "except ImportError as e:\n"
+            "    assert path in str(e) and 'hadoofus_amd.build' in str(e), e\n"
+            "else:\n"
+            "    raise SystemExit('a library that is not there was loaded')\n"
+            "assert m._lib is None\n"
+            "assert m.load() is m._lib is not None\n")
+    subprocess.check_call([sys.executable, "-c", code], cwd=ROOT)
+
+
+def test_a_wrong_abi_is_refused():
+    from hadoofus_read import md5crc_streams as m
+    other = types.SimpleNamespace(hdfs_md5crc_streams_abi_version=lambda: 2)
+    with pytest.raises(ImportError) as e:
+        m.check_abi(other)
+    assert "md5crc streams library ABI version 2, bindings written for 1" in str(e.value)
+    same = types.SimpleNamespace(hdfs_md5crc_streams_abi_version=lambda: 1)
+    assert m.check_abi(same) is same
+
+
+def test_entry_helper():
+    from hadoofus_read import md5crc_streams as m
+
+    class T:  # what companion.ptr takes of a torch tensor
+        def data_ptr(self):
+            return 0x1000
+
+        def numel(self):
+            return 10
+
+        def element_size(self):
+            return 1
+    assert m.entry(0x1000, 10) == dict(stream_ptr=0x1000, nbytes=10) == m.entry(T())
+    assert m.entry(T(), 4)["nbytes"] == 4 and m.entry() == dict(stream_ptr=None, nbytes=0)
+    arr = m.entries([m.entry(0x1000, 10)] * 2)
+    assert (arr[1].stream, arr[1].len, arr[1].nchunks) == (0x1000, 10, 0)
+    assert (m.MAX_ENTRIES, m.PATH_KERNEL, m.PATH_FALLBACK, m.TIME_NONE) == (1024, 0, 1, 0)
+
+
+# ---- rejections that need no device ---------------------------------------------------------------
+def _spoil(arr):
+    for e in arr:
+        e.rc, e.path, e.npkts, e.consumed, e.payload, e.nchunks, e.offset_in_block = 7, 7, 7, 7, 7, 7, 7
+        for i in range(16):
+            e.md5[i] = 7
+
+
+def _outs(arr):
+    return [(e.rc, e.path, e.npkts, e.consumed, e.payload, e.nchunks, e.offset_in_block, bytes(e.md5)) for e in arr]
+
+
+def test_rejections_without_a_device(ms):
+    lib = ms.load()
+    good = [ms.entry(0x1000, 1000)] * 3  # never dereferenced: every call is decided by its arguments
+    zero = (0, 0, 0, 0, 0, 0, 0, bytes(16))
+
+    def call(batch=good, n=None, proto=2, cs=512, ctype=2, arr=None, fc=False):
+        arr = ms.entries(batch) if arr is None else arr
+        _spoil(arr)
+        n = len(batch) if n is None else n
+        if fc:
+            rc = lib.hdfs_md5crc_streams_file_checksum(arr, n, proto, cs, ctype, None, ctypes.byref(ms.FileChecksum()))
+        else:
+            rc = lib.hdfs_md5crc_streams_block_digests(arr, n, proto, cs, ctype, None)
+        return rc, arr, lib.hdfs_md5crc_streams_last_error().decode()
+    for fc in (False, True):
+        for kw, text in ((dict(proto=0), "proto"), (dict(proto=3), "proto"), (dict(ctype=3), "checksum type"),
+                         (dict(ctype=-1), "checksum type"), (dict(ctype=0), "CRC32 or CRC32C"),
+                         (dict(cs=0), "chunk_size")):
+            rc, arr, err = call(fc=fc, **kw)
+            assert rc == EINVAL and "entry 0" in err and text in err and "device" not in err, (kw, err)
+            assert _outs(arr) == [zero] * 3, kw
+        rc, _, err = call(n=0, fc=fc)
+        assert rc == EINVAL and "no entries" in err and "entry 0" in err
+        rc, _, err = call(n=ms.MAX_ENTRIES + 1, arr=(ms.Entry * (ms.MAX_ENTRIES + 1))(), fc=fc)
+        assert rc == EINVAL and "1025 entries" in err and "entry 1024" in err
+        rc, arr, err = call([good[0], ms.entry(None, 5)], fc=fc)
+        assert rc == EINVAL and "entry 1" in err and "stream" in err and _outs(arr) == [zero] * 2
+    assert lib.hdfs_md5crc_streams_block_digests(None, 3, 2, 512, 2, None) == EINVAL
+    assert lib.hdfs_md5crc_streams_file_checksum(None, 3, 2, 512, 2, None, None) == EINVAL
+    with pytest.raises(ms.abi.CRC32CError) as e:  # through the bindings: the call's own refusal raises
+        ms.block_digests(good, proto=7)
+    assert e.value.code == EINVAL and "proto" in str(e.value)
+    with pytest.raises(ms.abi.CRC32CError):
+        ms.file_checksum(good, ctype=0)
+
+
+def test_timing_argument_errors(ms):
+    lib, out = ms.load(), ctypes.c_double(5)
+    one = [ms.entry(0x1000, 100)]
+
+    def call(flags=0, iters=1, res=ctypes.byref(out), proto=2):
+        rc = lib.hdfs_md5crc_streams_time(ms.entries(one), 1, proto, 512, 2, flags, iters, res)
+        return rc, lib.hdfs_md5crc_streams_last_error()
+    # every one decided before a device is asked (0x1000 is no device memory: going on would say so)
+    for kw in (dict(iters=0), dict(iters=-3), dict(res=None)):
+        rc, err = call(**kw)
+        assert rc == EINVAL and b"iters" in err and b"device" not in err, (kw, err)
+    assert call(proto=7)[0] == EINVAL
+    for flags in (1, 2, 1 << 8, 1 << 31):
+        rc, err = call(flags=flags)
+        assert rc == EINVAL and b"flags" in err and b"device" not in err, (flags, err)
+    assert out.value == 0  # set to 0 by every call that was given it
+
+
+def test_last_error_text_is_its_own(ms):
+    from hadoofus_read import read_batch as rb
+    rl, lib = rb.load(), ms.load()
+    assert rl.hdfs_read_batch_read_blocks(rb.entries([rb.entry(0x1000, 5, 0x2000, 5)]), 1, 7, 512, 2, None, 0,
+                                          None) == EINVAL
+    before = rl.hdfs_read_batch_last_error()
+    assert lib.hdfs_md5crc_streams_block_digests(ms.entries([ms.entry(0x1000, 5)]), 1, 2, 0, 2, None) == EINVAL
+    assert lib.hdfs_md5crc_streams_last_error() == b"entry 0: chunk_size 0"
+    assert rl.hdfs_read_batch_last_error() == before == b"entry 0: proto must be 1 or 2"
+
+
+# ---- the kernels' metadata --------------------------------------------------------------------------
+def test_kernel_metadata(tmp_path):
+    """hipcc -S of the kernel file: no kernel has a private segment (no scratch:
+    the digest's descriptor, cursor and two blocks of sixteen words all live in
+    registers), the digest is one wave a workgroup without LDS, the header check
+    four waves with a 64-byte expected header each, the probe one workgroup of
+    1 024 with its two count arrays."""
+    from hadoofus_amd import build
+    asm = tmp_path / "md5crc_streams_kernels.s"
+    subprocess.check_call([build._hipcc(), f"--offload-arch={build.ARCH}", "-O3", "-std=c++17", "--cuda-device-only",
+                           "-S", f"-I{build.INCLUDE}", f"-I{build.CSRC}",
+                           os.path.join(build.CSRC, "md5crc_streams_kernels.hip"), "-o", str(asm)])
+    txt = asm.read_text()
+    meta = {}
+    for block in txt.split("  - .agpr_count:")[1:]:
+        name = re.search(r"\.name:\s+(\S+)", block).group(1)
+        meta[name] = {k: int(v) for k, v in re.findall(
+            r"\.(vgpr_count|sgpr_count|private_segment_fixed_size|group_segment_fixed_size|vgpr_spill_count|"
+            r"max_flat_workgroup_size):\s+(\d+)", block)}
+    assert len(meta) == 4
+    get = lambda part: next(v for k, v in meta.items() if part in k)  # noqa: E731
+    probe, check, digest, gather = (get(k) for k in ("probe_streams_kernel", "check_headers_kernel",
+                                                     "digest_streams_kernel", "gather_regions_kernel"))
+    for k in (probe, check, digest, gather):
+        assert k["private_segment_fixed_size"] == 0 and k["vgpr_spill_count"] == 0, k
+    assert probe["group_segment_fixed_size"] == 8192 and probe["max_flat_workgroup_size"] == 1024
+    assert probe["vgpr_count"] <= 128  # 1024 threads are 16 waves, four a SIMD
+    assert check["group_segment_fixed_size"] == 4 * 64 and check["max_flat_workgroup_size"] == 256
+    assert digest["group_segment_fixed_size"] == 0 and digest["max_flat_workgroup_size"] == 64
+    assert gather["group_segment_fixed_size"] == 0 and gather["max_flat_workgroup_size"] == 64
+    assert (digest["vgpr_count"], digest["sgpr_count"]) == DIGEST_REGISTERS
+    # the digest reads global memory, never through a flat or a buffer instruction, and stores 16 bytes once
+    body = txt.split("digest_streams_kernel", 2)[-1].split(".end_amdhsa_kernel")[0]
+    assert "global_load_dwordx4" in body and "flat_load" not in body and "buffer_load" not in body
+
+
+DIGEST_REGISTERS = (111, 102)  # VGPRs, SGPRs of digest_streams_kernel
