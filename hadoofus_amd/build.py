@@ -91,6 +91,17 @@ md5_core.h and the cursor of md5crc_streams_lookup.h over the packets' CRC
 regions, and hands what is not of the regular shape to
 hdfs_crc32c_parse_packets.  It links neither the MD5CRC library nor any other
 companion.  Its bindings are hadoofus_read/md5crc_streams.py.
+
+Composite CRCs taken from packet streams have a sixth table, CRC_LIBRARIES, rows
+of that shape: libhadoofus_crc_streams.so (include/hadoofus_crc_streams.h) is
+built with the others, the same way, from its own sources and export map.  It
+folds the chunk CRCs where they lie inside the wire streams into block CRCs
+(HDFS's COMPOSITE_CRC mode): the read batch's probe arithmetic
+(read_batch_layout.h) and header comparison (read_batch_header.h,
+read_batch_verify.h), the GF(2) arithmetic of crc_streams_lookup.h with
+multipliers made by crc32c_tables.h's operator, and hands what is not of the
+regular shape to hdfs_crc32c_parse_packets.  It links no other companion.  Its
+bindings are hadoofus_read/crc_streams.py.
 """
 import os
 import subprocess
@@ -225,6 +236,18 @@ MD5CRC_STREAMS_PUBLIC = ["hadoofus_md5crc_streams.h", "hadoofus_md5crc.h", "hado
 DIGEST_LIBRARIES = (
     ("md5crc_streams", MD5CRC_STREAMS_SOURCES, MD5CRC_STREAMS_HEADERS, MD5CRC_STREAMS_PUBLIC),
 )
+CRC_STREAMS_LIB = companion_lib("crc_streams")
+CRC_STREAMS_SOURCES = ["crc_streams_kernels.hip", "crc_streams.cpp"]
+CRC_STREAMS_HEADERS = ["crc_streams_internal.h", "crc_streams_lookup.h", "read_batch_layout.h", "read_batch_header.h",
+                       "read_batch_verify.h", "wire_fused_batch_lookup.h", "wire_fused_round.h", "wire_fused_crc.h",
+                       "wire_internal.h", "crc32c_frame.h", "crc32c_outpkt.h", "crc32c_tables.h",
+                       "companion_support.h", "crc_streams_exports.map"]
+CRC_STREAMS_PUBLIC = ["hadoofus_crc_streams.h", "hadoofus_crc32c.h"]
+# The libraries that combine the CRCs of packet streams, rows as in COMPANIONS; their bindings are
+# hadoofus_read/<stem>.py.
+CRC_LIBRARIES = (
+    ("crc_streams", CRC_STREAMS_SOURCES, CRC_STREAMS_HEADERS, CRC_STREAMS_PUBLIC),
+)
 ARCH = os.environ.get("HADOOFUS_OFFLOAD_ARCH", "gfx950")
 
 
@@ -267,8 +290,9 @@ def build(force=False, verbose=False, diag=True):
     in parallel), then the MD5CRC, gather-write, wire-stream, wire-batch,
     gather-wire, fused-wire, fused-wire-batch, fused-gather-wire and
     fused-gather-wire-batch companions, the read side's libraries, the
-    positional-read libraries, the scatter-read libraries and the libraries
-    that digest packet streams (in parallel).
+    positional-read libraries, the scatter-read libraries, the libraries
+    that digest packet streams and the libraries that combine their CRCs (in
+    parallel).
     Returns the release library's path."""
     os.makedirs(LIBDIR, exist_ok=True)
     jobs = []
@@ -287,7 +311,8 @@ def build(force=False, verbose=False, diag=True):
         os.replace(out + ".tmp", out)
     # the companions link against the release library, so after it is in place
     procs = []
-    for stem, sources, headers, public in COMPANIONS + READ_LIBRARIES + PREAD_LIBRARIES + PREADV_LIBRARIES + DIGEST_LIBRARIES:
+    for stem, sources, headers, public in COMPANIONS + READ_LIBRARIES + PREAD_LIBRARIES + PREADV_LIBRARIES + DIGEST_LIBRARIES + \
+            CRC_LIBRARIES:
         out = companion_lib(stem)
         if force or _stale(out, sources, headers, public, [LIB]):
             cmd = _companion_cmd(out + ".tmp", sources, f"{stem}_exports.map")

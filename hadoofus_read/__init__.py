@@ -15,9 +15,14 @@ fragments) lives in libhadoofus_preadv_batch.so, built and loaded the same way
 digests and the file checksum taken from packet streams
 (include/hadoofus_md5crc_streams.h: the chunk CRCs digested where they lie in
 the streams) live in libhadoofus_md5crc_streams.so, built and loaded the same
-way (md5crc_streams.py, the module hadoofus_read.md5crc_streams).  Importing
+way (md5crc_streams.py, the module hadoofus_read.md5crc_streams).  The
+composite CRCs of blocks and files taken from the same streams
+(include/hadoofus_crc_streams.h: the chunk CRCs folded where they lie, HDFS's
+COMPOSITE_CRC mode) live in libhadoofus_crc_streams.so, built and loaded the
+same way (crc_streams.py, the module hadoofus_read.crc_streams).  Importing
 the package loads nothing.
 """
+from . import crc_streams  # noqa: F401  (binds nothing until first use)
 from . import md5crc_streams  # noqa: F401  (binds nothing until first use)
 from . import pread_batch  # noqa: F401  (binds nothing until first use)
 from . import preadv_batch  # noqa: F401  (binds nothing until first use)
