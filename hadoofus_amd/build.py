@@ -102,6 +102,19 @@ read_batch_verify.h), the GF(2) arithmetic of crc_streams_lookup.h with
 multipliers made by crc32c_tables.h's operator, and hands what is not of the
 regular shape to hdfs_crc32c_parse_packets.  It links no other companion.  Its
 bindings are hadoofus_read/crc_streams.py.
+
+Reads re-framed as writes have a seventh table, RELAY_LIBRARIES, rows of that
+shape: libhadoofus_relay_batch.so (include/hadoofus_relay_batch.h) is built
+with the others, the same way, from its own sources and export map.  It runs
+the fused round once for both sides (wire_fused_round.h): the registers are
+loaded from a read's packet stream at the places relay_batch_lookup.h gives,
+verified with the read batch's comparisons (read_batch_verify.h,
+read_batch_header.h) from its probe arithmetic (read_batch_layout.h), and
+stored as the packets of a write, found with wire_fused_batch_lookup.h.  What
+it does not take it hands to hdfs_crc32c_read_packets and then to the fused
+batch write library's kernel, wire_fused_batch_kernels.hip, compiled into it as
+it stands (as the gather-wire library compiles writev_kernels.hip).  It links
+no other companion.  Its bindings are hadoofus_read/relay_batch.py.
 """
 import os
 import subprocess
@@ -248,6 +261,19 @@ CRC_STREAMS_PUBLIC = ["hadoofus_crc_streams.h", "hadoofus_crc32c.h"]
 CRC_LIBRARIES = (
     ("crc_streams", CRC_STREAMS_SOURCES, CRC_STREAMS_HEADERS, CRC_STREAMS_PUBLIC),
 )
+RELAY_BATCH_LIB = companion_lib("relay_batch")
+RELAY_BATCH_SOURCES = ["relay_batch_kernels.hip", "wire_fused_batch_kernels.hip", "relay_batch.cpp"]
+RELAY_BATCH_HEADERS = ["relay_batch_internal.h", "relay_batch_lookup.h", "read_batch_layout.h", "read_batch_header.h",
+                       "read_batch_verify.h", "wire_fused_batch_internal.h", "wire_fused_batch_lookup.h",
+                       "wire_fused_round.h", "wire_fused_crc.h", "wire_fused_tables.h", "wire_fused_host.h",
+                       "wire_internal.h", "wire_layout.h", "crc32c_frame.h", "crc32c_outpkt.h", "crc32c_tables.h",
+                       "companion_support.h", "relay_batch_exports.map"]
+RELAY_BATCH_PUBLIC = ["hadoofus_relay_batch.h", "hadoofus_crc32c.h"]
+# The libraries that connect the read side to the write side, rows as in COMPANIONS; their bindings are
+# hadoofus_read/<stem>.py.
+RELAY_LIBRARIES = (
+    ("relay_batch", RELAY_BATCH_SOURCES, RELAY_BATCH_HEADERS, RELAY_BATCH_PUBLIC),
+)
 ARCH = os.environ.get("HADOOFUS_OFFLOAD_ARCH", "gfx950")
 
 
@@ -291,8 +317,8 @@ def build(force=False, verbose=False, diag=True):
     gather-wire, fused-wire, fused-wire-batch, fused-gather-wire and
     fused-gather-wire-batch companions, the read side's libraries, the
     positional-read libraries, the scatter-read libraries, the libraries
-    that digest packet streams and the libraries that combine their CRCs (in
-    parallel).
+    that digest packet streams, the libraries that combine their CRCs and the
+    libraries that relay a read into a write (in parallel).
     Returns the release library's path."""
     os.makedirs(LIBDIR, exist_ok=True)
     jobs = []
@@ -312,7 +338,7 @@ def build(force=False, verbose=False, diag=True):
     # the companions link against the release library, so after it is in place
     procs = []
     for stem, sources, headers, public in COMPANIONS + READ_LIBRARIES + PREAD_LIBRARIES + PREADV_LIBRARIES + DIGEST_LIBRARIES + \
-            CRC_LIBRARIES:
+            CRC_LIBRARIES + RELAY_LIBRARIES:
         out = companion_lib(stem)
         if force or _stale(out, sources, headers, public, [LIB]):
             cmd = _companion_cmd(out + ".tmp", sources, f"{stem}_exports.map")

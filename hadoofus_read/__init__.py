@@ -19,13 +19,18 @@ way (md5crc_streams.py, the module hadoofus_read.md5crc_streams).  The
 composite CRCs of blocks and files taken from the same streams
 (include/hadoofus_crc_streams.h: the chunk CRCs folded where they lie, HDFS's
 COMPOSITE_CRC mode) live in libhadoofus_crc_streams.so, built and loaded the
-same way (crc_streams.py, the module hadoofus_read.crc_streams).  Importing
-the package loads nothing.
+same way (crc_streams.py, the module hadoofus_read.crc_streams).  A batch of
+verified reads re-framed as writes (include/hadoofus_relay_batch.h: each
+stream's payload verified and written out again as a write's packet stream in
+one pass) lives in libhadoofus_relay_batch.so, built and loaded the same way
+(relay_batch.py, the module hadoofus_read.relay_batch).  Importing the package
+loads nothing.
 """
 from . import crc_streams  # noqa: F401  (binds nothing until first use)
 from . import md5crc_streams  # noqa: F401  (binds nothing until first use)
 from . import pread_batch  # noqa: F401  (binds nothing until first use)
 from . import preadv_batch  # noqa: F401  (binds nothing until first use)
+from . import relay_batch  # noqa: F401  (binds nothing until first use)
 from .read_batch import (  # noqa: F401  (binds nothing until first use)
     ABI_VERSION, LIB_PATH, MAX_ENTRIES, MAX_GROUPS, PATH_FALLBACK, PATH_KERNEL, Entry, entry, read_blocks, time,
     time_groups,
