@@ -115,6 +115,10 @@ it does not take it hands to hdfs_crc32c_read_packets and then to the fused
 batch write library's kernel, wire_fused_batch_kernels.hip, compiled into it as
 it stands (as the gather-wire library compiles writev_kernels.hip).  It links
 no other companion.  Its bindings are hadoofus_read/relay_batch.py.
+
+The six read-side libraries share the host skeleton of a probed batch call,
+read_batch_host.h (the run, the entries' outcomes, the main library's read and
+walk with unlimited record room, the scratch), compiled into each.
 """
 import os
 import subprocess
@@ -208,7 +212,7 @@ READ_BATCH_SOURCES = ["read_batch_kernels.hip", "read_batch.cpp"]
 READ_BATCH_HEADERS = ["read_batch_internal.h", "read_batch_layout.h", "wire_fused_batch_lookup.h", "wire_fused_round.h",
                       "wire_fused_crc.h", "wire_fused_tables.h", "wire_fused_host.h", "wire_internal.h",
                       "crc32c_frame.h", "crc32c_outpkt.h", "crc32c_tables.h", "companion_support.h",
-                      "read_batch_verify.h", "read_batch_exports.map"]
+                      "read_batch_host.h", "read_batch_verify.h", "read_batch_exports.map"]
 READ_BATCH_PUBLIC = ["hadoofus_read_batch.h", "hadoofus_crc32c.h"]
 # The read side's libraries, rows as in COMPANIONS; their bindings are hadoofus_read/<stem>.py.
 READ_LIBRARIES = (
@@ -219,7 +223,7 @@ PREAD_BATCH_SOURCES = ["pread_batch_kernels.hip", "pread_batch.cpp"]
 PREAD_BATCH_HEADERS = ["pread_batch_internal.h", "pread_batch_layout.h", "read_batch_layout.h", "read_batch_verify.h",
                        "wire_fused_batch_lookup.h", "wire_fused_round.h", "wire_fused_crc.h", "wire_fused_tables.h",
                        "wire_fused_host.h", "wire_internal.h", "crc32c_frame.h", "crc32c_outpkt.h", "crc32c_tables.h",
-                       "companion_support.h", "pread_batch_exports.map"]
+                       "companion_support.h", "read_batch_host.h", "pread_batch_exports.map"]
 PREAD_BATCH_PUBLIC = ["hadoofus_pread_batch.h", "hadoofus_crc32c.h"]
 # The positional-read libraries, rows as in COMPANIONS; their bindings are hadoofus_read/<stem>.py.
 PREAD_LIBRARIES = (
@@ -232,7 +236,7 @@ PREADV_BATCH_HEADERS = ["preadv_batch_internal.h", "preadv_batch_lookup.h", "rea
                         "wirev_fused_internal.h", "wirev_fused_lookup.h", "wire_fused_batch_lookup.h",
                         "wire_fused_round.h", "wire_fused_crc.h", "wire_fused_tables.h", "wire_fused_host.h",
                         "wire_internal.h", "crc32c_frame.h", "crc32c_outpkt.h", "crc32c_tables.h",
-                        "companion_support.h", "preadv_batch_exports.map"]
+                        "companion_support.h", "read_batch_host.h", "preadv_batch_exports.map"]
 PREADV_BATCH_PUBLIC = ["hadoofus_preadv_batch.h", "hadoofus_crc32c.h"]
 # The scatter-read libraries, rows as in COMPANIONS; their bindings are hadoofus_read/<stem>.py.
 PREADV_LIBRARIES = (
@@ -243,7 +247,8 @@ MD5CRC_STREAMS_SOURCES = ["md5crc_streams_kernels.hip", "md5crc_streams.cpp"]
 MD5CRC_STREAMS_HEADERS = ["md5crc_streams_internal.h", "md5crc_streams_lookup.h", "md5_core.h", "read_batch_layout.h",
                           "read_batch_header.h", "read_batch_verify.h", "wire_fused_batch_lookup.h",
                           "wire_fused_round.h", "wire_fused_crc.h", "wire_internal.h", "crc32c_frame.h",
-                          "crc32c_outpkt.h", "companion_support.h", "md5crc_streams_exports.map"]
+                          "crc32c_outpkt.h", "companion_support.h", "read_batch_host.h",
+                          "md5crc_streams_exports.map"]
 MD5CRC_STREAMS_PUBLIC = ["hadoofus_md5crc_streams.h", "hadoofus_md5crc.h", "hadoofus_crc32c.h"]
 # The libraries that digest packet streams, rows as in COMPANIONS; their bindings are hadoofus_read/<stem>.py.
 DIGEST_LIBRARIES = (
@@ -254,7 +259,7 @@ CRC_STREAMS_SOURCES = ["crc_streams_kernels.hip", "crc_streams.cpp"]
 CRC_STREAMS_HEADERS = ["crc_streams_internal.h", "crc_streams_lookup.h", "read_batch_layout.h", "read_batch_header.h",
                        "read_batch_verify.h", "wire_fused_batch_lookup.h", "wire_fused_round.h", "wire_fused_crc.h",
                        "wire_internal.h", "crc32c_frame.h", "crc32c_outpkt.h", "crc32c_tables.h",
-                       "companion_support.h", "crc_streams_exports.map"]
+                       "companion_support.h", "read_batch_host.h", "crc_streams_exports.map"]
 CRC_STREAMS_PUBLIC = ["hadoofus_crc_streams.h", "hadoofus_crc32c.h"]
 # The libraries that combine the CRCs of packet streams, rows as in COMPANIONS; their bindings are
 # hadoofus_read/<stem>.py.
@@ -267,7 +272,7 @@ RELAY_BATCH_HEADERS = ["relay_batch_internal.h", "relay_batch_lookup.h", "read_b
                        "read_batch_verify.h", "wire_fused_batch_internal.h", "wire_fused_batch_lookup.h",
                        "wire_fused_round.h", "wire_fused_crc.h", "wire_fused_tables.h", "wire_fused_host.h",
                        "wire_internal.h", "wire_layout.h", "crc32c_frame.h", "crc32c_outpkt.h", "crc32c_tables.h",
-                       "companion_support.h", "relay_batch_exports.map"]
+                       "companion_support.h", "read_batch_host.h", "relay_batch_exports.map"]
 RELAY_BATCH_PUBLIC = ["hadoofus_relay_batch.h", "hadoofus_crc32c.h"]
 # The libraries that connect the read side to the write side, rows as in COMPANIONS; their bindings are
 # hadoofus_read/<stem>.py.

@@ -1,21 +1,24 @@
-// Host support shared by the nine companion libraries of
-// libhadoofus_crc32c.so (md5crc.cpp, writev.cpp and the seven wire-stream
-// libraries wire*.cpp): the last-error text, the engine's device, grow-only
+// Host support shared by the fifteen companion libraries of
+// libhadoofus_crc32c.so (md5crc.cpp, writev.cpp, the seven wire-stream
+// libraries wire*.cpp and the six read-side libraries, which add
+// read_batch_host.h): the last-error text, the engine's device, grow-only
 // buffers, a device table with its pinned staging twin, scratch bound to a
 // device with the two events of a timing call, where a pointer lives, the
-// packet argument check and the "always synchronise, then report" tail of a
-// call.  Host only: no kernel file includes it.  Every library's export map
-// keeps all of this local, so each library has its own copy, its own
-// last-error text included.
+// overlap sweep over the buffers of a batch, the packet argument check and the
+// "always synchronise, then report" tail of a call.  Host only: no kernel file
+// includes it.  Every library's export map keeps all of this local, so each
+// library has its own copy, its own last-error text included.
 #ifndef HADOOFUS_COMPANION_SUPPORT_H
 #define HADOOFUS_COMPANION_SUPPORT_H
 
 #include <hip/hip_runtime_api.h>
 
+#include <algorithm>
 #include <cstdarg>
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
+#include <vector>
 
 #include "hadoofus_crc32c.h"
 
@@ -301,6 +304,82 @@ inline int check_places(const hdfs_crc32c_iovec *iov, int n, const void *wire, u
       return fail(HDFS_CRC32C_EINVAL, "fragment %d and wire overlap", i);
   }
   return HDFS_CRC32C_OK;
+}
+
+// ---- the buffers of a batch: no writer over another writer or over any reader --------------
+// A batch names ranges a kernel writes (a write's stream, a read's destination)
+// and ranges it only reads (a write's data, a read's stream).  No written range
+// may overlap another written range or a read one; read ranges may overlap each
+// other.  The intervals sorted by their first byte, then one pass that remembers
+// the furthest end among the written and among the read ranges seen so far.
+struct Span {
+  uintptr_t lo, hi;  // [lo, hi), not empty
+  uint32_t k;        // entry
+  uint32_t wire;     // 1: a written range
+};
+
+// The sweep's order; a caller with very many spans may hand them over in it.
+inline bool span_before(const Span &a, const Span &b) {
+  return a.lo != b.lo ? a.lo < b.lo : (a.wire != b.wire ? a.wire > b.wire : a.k < b.k);
+}
+
+// The two nouns of a refusal: "entry 3: <writer> overlaps the <writer|reader> of entry 1".
+struct SpanNouns {
+  const char *writer = "wire", *reader = "data";
+};
+
+// The sweep itself.  next() hands over the spans in the sweep's order, NULL at
+// the end.  hit_wire / hit_other (may be NULL): on a refusal, the written range
+// and the range it overlaps, for a caller whose ranges are more than one per
+// entry and who names the one at fault.
+template <class Next>
+int sweep_spans(Next next, Span *hit_wire, Span *hit_other, SpanNouns nouns) {
+  const auto refuse = [&](const Span &wire, const Span &other, uint32_t a, uint32_t b) {
+    if (hit_wire) *hit_wire = wire;
+    if (hit_other) *hit_other = other;
+    return fail(HDFS_CRC32C_EINVAL, "entry %u: %s overlaps the %s of entry %u", a, nouns.writer,
+                other.wire ? nouns.writer : nouns.reader, b);
+  };
+  const Span *far_w = nullptr, *far_d = nullptr;
+  while (const Span *s = next()) {
+    // every span ahead of s starts at or below s->lo: it overlaps s iff it ends behind s->lo
+    if (far_w && far_w->hi > s->lo)  // writer over writer: the later entry is the one refused
+      return s->wire ? refuse(*far_w, *s, std::max(far_w->k, s->k), std::min(far_w->k, s->k))
+                     : refuse(*far_w, *s, far_w->k, s->k);
+    if (s->wire && far_d && far_d->hi > s->lo) return refuse(*s, *far_d, s->k, far_d->k);
+    const Span *&far = s->wire ? far_w : far_d;
+    if (!far || s->hi > far->hi) far = s;
+  }
+  return HDFS_CRC32C_OK;
+}
+
+inline void sort_spans(std::vector<Span> &v) {  // one pass where they come in the sweep's order already
+  if (!std::is_sorted(v.begin(), v.end(), span_before)) std::sort(v.begin(), v.end(), span_before);
+}
+
+// Written and read ranges in one array.
+inline int check_overlaps(std::vector<Span> &v, Span *hit_wire = nullptr, Span *hit_other = nullptr,
+                          SpanNouns nouns = SpanNouns{}) {
+  sort_spans(v);
+  size_t i = 0;
+  return sweep_spans([&] { return i < v.size() ? &v[i++] : nullptr; }, hit_wire, hit_other, nouns);
+}
+
+// The written ranges and the read ranges apart, as the read side collects them:
+// each array is sorted only where it does not rise already (the ranges of a
+// batch laid out in order cost a pass, not a sort), and the two are merged as
+// the sweep goes, a written range ahead of a read one that starts at its byte.
+inline int check_overlaps(std::vector<Span> &writers, std::vector<Span> &readers, Span *hit_wire = nullptr,
+                          Span *hit_other = nullptr, SpanNouns nouns = SpanNouns{}) {
+  sort_spans(writers);
+  sort_spans(readers);
+  size_t i = 0, j = 0;
+  return sweep_spans(
+      [&]() -> const Span * {
+        if (i < writers.size() && (j >= readers.size() || !span_before(readers[j], writers[i]))) return &writers[i++];
+        return j < readers.size() ? &readers[j++] : nullptr;
+      },
+      hit_wire, hit_other, nouns);
 }
 
 // ---- the arguments of a packet run -----------------------------------------------------

@@ -9,7 +9,8 @@
 // synchronise: this file holds no walk of its own.  The records of that walk
 // become a per-packet table that the same kernels fold and reduce.  The host
 // combines only whole blocks (hdfs_crc_streams_combine), with
-// crc32c_tables.h's operator.
+// crc32c_tables.h's operator.  The run, the walk in pieces and the collection
+// of the entries' outcomes are read_batch_host.h's.
 #include <hip/hip_runtime.h>
 
 #include <mutex>
@@ -20,6 +21,7 @@
 #include "crc_streams_internal.h"
 #include "crc_streams_lookup.h"
 #include "hadoofus_crc_streams.h"
+#include "read_batch_host.h"
 #include "read_batch_layout.h"
 
 namespace hdfs_crc_streams {
@@ -30,8 +32,6 @@ using namespace hdfs_companion;
 static_assert(HDFS_CRC_STREAMS_MAX_ENTRIES == kMaxEntries, "the header's limit is the probe's");
 static_assert(sizeof(hdfs_crc_streams_entry) == 72, "the ABI of version 1");
 static_assert(sizeof(struct hdfs_crc_streams_file_checksum) == 24, "the ABI of version 1");
-
-constexpr size_t kPieceRecords = 65536;  // records of one hdfs_crc32c_parse_packets call of the fallback
 
 uint32_t poly_of(int ctype) { return ctype == HDFS_CRC32C_CSUM_CRC32 ? hdfs_crc32c::kPolyZlib : hdfs_crc32c::kPoly; }
 
@@ -98,17 +98,6 @@ int check_arguments(hdfs_crc_streams_entry *e, size_t n, int proto, uint32_t chu
   return HDFS_CRC32C_OK;
 }
 
-// Every stream inside one allocation of device `dev`.
-int check_batch_places(const hdfs_crc_streams_entry *e, size_t n, int dev) {
-  Allocations al;
-  for (size_t b = 0; b < n; b++) {
-    if (!e[b].len) continue;
-    const int rc = al.check(e[b].stream, e[b].len, dev, "stream");
-    if (rc) return prefix_fail(rc, "entry %zu", b);
-  }
-  return HDFS_CRC32C_OK;
-}
-
 // ---- an entry handed to the main library ------------------------------------------------
 // What the fallback collects for its launches.
 struct Fallback {
@@ -117,47 +106,28 @@ struct Fallback {
   std::vector<PktRec> pkts;
 };
 
-// hdfs_crc32c_parse_packets of the entry's stream with unlimited record room,
-// in pieces of kPieceRecords records: a piece that filled its room and ended
-// neither in an error nor in the empty last packet goes on where it stopped.
+// The walk of the entry's stream (walk_pieces): every packet with CRCs becomes
+// a record of the per-packet table.
 int walk_entry(hdfs_crc_streams_entry &x, size_t b, int proto, uint32_t chunk_size, int ctype, Fallback &f) {
   x.path = HDFS_CRC_STREAMS_PATH_FALLBACK;
   const uint8_t *s = static_cast<const uint8_t *>(x.stream);
   const size_t first_pkt = f.pkts.size();
-  uint64_t pos = 0, nchunks = 0;
-  int rc = 0;
-  if (g_s.recs.size() < kPieceRecords) g_s.recs.resize(kPieceRecords);
-  while (pos < x.len) {
-    size_t np = 0;
-    uint64_t used = 0;
-    rc = hdfs_crc32c_parse_packets(s + pos, x.len - pos, proto, chunk_size, ctype, g_s.recs.data(), kPieceRecords, &np,
-                                   &used);
-    if (rc < 0) {
-      x.rc = rc;
-      f.pkts.resize(first_pkt);
-      return engine_fail(rc, "parse_packets"), prefix_fail(rc, "entry %zu", b);
-    }
-    for (size_t i = 0; i < np; i++) {
-      const hdfs_crc32c_packet &k = g_s.recs[i];
-      if (!x.npkts && !i) x.offset_in_block = k.offset_in_block;
-      if (k.error) continue;
-      x.payload += uint64_t(k.data_len);
-      if (k.crc_len > 0) {
-        f.pkts.push_back(PktRec{reinterpret_cast<uintptr_t>(s) + pos + k.stream_off + k.header_len, 0u,
-                                uint32_t(k.crc_len) / 4u, uint32_t(k.data_len)});
-        nchunks += uint32_t(k.crc_len) / 4u;
-      }
-    }
-    x.npkts += np;
-    pos += used;
-    const bool ended = np && g_s.recs[np - 1].data_len == 0;  // the empty last packet ends the walk
-    if (rc || np < kPieceRecords || ended || !used) break;
-  }
-  x.consumed = pos;
-  x.rc = rc;
-  if (rc) {  // a framing error: no CRC
+  uint64_t nchunks = 0;
+  const Walk w = walk_pieces(g_s.recs, kPieceRecords, s, x.len, b, proto, chunk_size, ctype,
+                             [&](const hdfs_crc32c_packet &k, uint64_t at) {
+                               if (k.crc_len <= 0) return;
+                               f.pkts.push_back(PktRec{reinterpret_cast<uintptr_t>(s) + at + k.stream_off + k.header_len,
+                                                       0u, uint32_t(k.crc_len) / 4u, uint32_t(k.data_len)});
+                               nchunks += uint32_t(k.crc_len) / 4u;
+                             });
+  x.npkts = w.npkts;
+  x.payload = w.payload;
+  x.offset_in_block = w.offset_in_block;
+  x.rc = w.rc;
+  if (w.rc >= 0) x.consumed = w.pos;
+  if (w.rc) {  // the engine's failure, or a framing error: no CRC
     f.pkts.resize(first_pkt);
-    return rc;
+    return w.rc;
   }
   const size_t npk = f.pkts.size() - first_pkt;
   if (f.pkts.size() > hdfs_read_batch::kMaxPackets) {
@@ -219,13 +189,13 @@ int block_crcs(hdfs_crc_streams_entry *e, size_t n, int proto, uint32_t chunk_si
   int rc = check_arguments(e, n, proto, chunk_size, ctype);
   if (rc) return rc;
   if (timing) {  // decided by the arguments alone, before any device is asked
-    if (iters < 1 || !ms_per_iter) return fail(HDFS_CRC32C_EINVAL, "iters >= 1 and ms_per_iter are needed");
+    if ((rc = timing_args_ok(iters, ms_per_iter))) return rc;
     if (flags != HDFS_CRC_STREAMS_TIME_NONE) return fail(HDFS_CRC32C_EINVAL, "unknown timing flags 0x%x", flags);
   }
   int dev = -1;
   if ((rc = engine_device(&dev))) return rc;
   DeviceGuard g(dev);
-  if ((rc = check_batch_places(e, n, dev))) return rc;
+  if ((rc = check_stream_places(e, n, dev))) return rc;
   const Tables T(n);
   // the per-packet table, sized from the lengths alone: the probe has not run
   uint64_t all = 0, bound = 0;
@@ -256,38 +226,21 @@ int block_crcs(hdfs_crc_streams_entry *e, size_t n, int proto, uint32_t chunk_si
     if (le == hipSuccess) le = launch_reduce_streams(dv, uint32_t(n), cp, cap, st);
     return le;
   };
-  hipError_t he = hipMemcpyAsync(dv + T.in, pin + T.in, T.desc - T.in, hipMemcpyHostToDevice, st);
-  if (he == hipSuccess) he = launches();
-  if (he == hipSuccess) he = hipMemcpyAsync(pin + T.desc, dv + T.desc, T.bytes - T.desc, hipMemcpyDeviceToHost, st);
-  if (he == hipSuccess && timing) {
-    he = hipEventRecord(g_s.ev[0], st);
-    for (int i = 0; i < iters && he == hipSuccess; i++) he = launches();
-    if (he == hipSuccess) he = hipEventRecord(g_s.ev[1], st);
-  }
-  // always synchronised, even after an error: the tables are out of the device's use before the lock goes
-  const hipError_t se = hipStreamSynchronize(st);
-  if (he == hipSuccess) he = se;
-  if (he != hipSuccess) return fail(HDFS_CRC32C_EHIP, "crc streams: %s", hipGetErrorString(he));
-  if (timing) {
-    float ms = 0;
-    if ((he = hipEventElapsedTime(&ms, g_s.ev[0], g_s.ev[1])) != hipSuccess)
-      return fail(HDFS_CRC32C_EHIP, "crc streams: %s", hipGetErrorString(he));
-    *ms_per_iter = double(ms) / iters;
-  }
+  if ((rc = probed_run(st, g_s.tab, T.in, T.desc - T.in, T.desc, T.bytes, g_s.ev, timing ? iters : 0, ms_per_iter,
+                       "crc streams", launches)))
+    return rc;
   const Desc *desc = reinterpret_cast<const Desc *>(pin + T.desc);
   const uint32_t *crc = reinterpret_cast<const uint32_t *>(pin + T.crc);
   const uint32_t *slot = reinterpret_cast<const uint32_t *>(pin + T.slot);
   const uint32_t *status = reinterpret_cast<const uint32_t *>(pin + T.status);
   const uint32_t *pk0 = reinterpret_cast<const uint32_t *>(pin + T.pk0);
   const uint32_t nreg = reinterpret_cast<const uint32_t *>(pin + T.meta)[0];
-  int first_neg = 0, first_pos = 0;
-  char neg_text[sizeof(g_err)] = "";
+  Outcomes out;
   Fallback f;
   for (size_t b = 0; b < n; b++) {
     hdfs_crc_streams_entry &x = e[b];
     const uint32_t s = slot[b];
-    if (s != kNoSlot && (s >= nreg || desc[s].entry != b))
-      return fail(HDFS_CRC32C_EHIP, "internal: the probe's tables do not add up at entry %zu", b);
+    if (!slot_adds_up(s, kNoSlot, nreg, b, [&](uint32_t i) { return desc[i].entry; })) return tables_fail(b);
     if (s != kNoSlot && !status[s] && pk0[s + 1] <= cap) {
       const Desc &d = desc[s];
       x.rc = 0;
@@ -301,19 +254,10 @@ int block_crcs(hdfs_crc_streams_entry *e, size_t n, int proto, uint32_t chunk_si
       x.crc = crc[s];
       continue;
     }
-    const int r = walk_entry(x, b, proto, chunk_size, ctype, f);
-    if (r < 0 && !first_neg) {
-      first_neg = r;
-      std::memcpy(neg_text, g_err, sizeof(neg_text));
-    }
-    if (r > 0 && !first_pos) first_pos = r;
+    out.note(walk_entry(x, b, proto, chunk_size, ctype, f));
   }
   if ((rc = fold_fallbacks(e, f, reinterpret_cast<const uint32_t *>(dv + T.mult), st))) return rc;
-  if (first_neg) {
-    std::memcpy(g_err, neg_text, sizeof(neg_text));
-    return first_neg;
-  }
-  return first_pos;
+  return out.result();
 }
 
 int combine(const uint32_t *crcs, const uint64_t *lens, size_t n, int ctype, uint32_t *out) {

@@ -11,10 +11,10 @@
 // entry's own fragment list: this file holds no walk of its own.  The records
 // of a regular entry follow from its descriptor, cut by the probe to the
 // packets the read takes (pread_batch_layout.h; read_batch_layout.h:
-// packet_of, record_of).
+// packet_of, record_of).  The run, the collection of the entries' outcomes and
+// the scratch are read_batch_host.h's, the overlap sweep companion_support.h's.
 #include <hip/hip_runtime.h>
 
-#include <algorithm>
 #include <mutex>
 #include <vector>
 
@@ -22,6 +22,7 @@
 #include "hadoofus_preadv_batch.h"
 #include "pread_batch_layout.h"
 #include "preadv_batch_internal.h"
+#include "read_batch_host.h"
 #include "wire_fused_host.h"
 #include "wire_fused_tables.h"
 
@@ -43,20 +44,7 @@ static_assert(HDFS_PREADV_BATCH_MAX_ENTRIES == kMaxEntries, "the header's limit 
 // kernels or under the host's reading of them.
 std::mutex g_mu;
 using Fused = hdfs_wire_fused::DeviceState<prepare_unframe_scatter_batch, kBatchMaxGroups>;
-struct Scratch : DeviceScratch {
-  Fused fused;
-  TablePair tab;
-  std::vector<hdfs_crc32c_packet> recs;  // a fallback entry's records when the caller wants none
-
-  int reserve(int to, size_t tab_bytes) {
-    int rc = bind(to, "stream", [this] {
-      fused.release();
-      tab.release();
-    });
-    if (rc || (rc = fused.setup(to))) return rc;
-    return tab.reserve(tab_bytes, kTableFloor);
-  }
-} g_s;
+ReadScratch<Fused> g_s;
 
 void clear_outputs(hdfs_preadv_batch_entry *e, size_t n) {
   for (size_t b = 0; b < n; b++) {
@@ -129,85 +117,57 @@ int check_arguments(hdfs_preadv_batch_entry *e, size_t n, int proto, uint32_t ch
 // Every range inside one allocation of device `dev`; no non-empty fragment
 // overlaps a stream or another fragment of the batch, the same entry's
 // included.  A call may hold millions of fragments, so the overlaps are found
-// by one sweep over the ranges sorted by their first byte, not by comparing
-// every pair: a range overlaps an earlier one exactly when it starts below the
-// furthest end met so far, kept apart for the fragments and for the streams
-// (streams may overlap each other).
-struct Span {
-  uintptr_t lo, hi;
-  uint32_t entry;
-  int32_t frag;  // -1: the entry's stream
-};
-
-int overlap_fail(const Span &d, const Span &other) {
-  if (other.frag < 0)
-    return fail(HDFS_CRC32C_EINVAL, "entry %u: fragment %d overlaps the stream of entry %u", unsigned(d.entry),
-                int(d.frag), unsigned(other.entry));
-  const bool later = d.entry > other.entry || (d.entry == other.entry && d.frag > other.frag);
-  const Span &hi = later ? d : other, &lo = later ? other : d;
-  return fail(HDFS_CRC32C_EINVAL, "entry %u: fragment %d overlaps fragment %d of entry %u", unsigned(hi.entry),
-              int(hi.frag), int(lo.frag), unsigned(lo.entry));
-}
-
+// by one sweep over the sorted ranges (check_overlaps, one Span per fragment
+// and per stream), not by comparing every pair.
 int check_batch_places(const hdfs_preadv_batch_entry *e, size_t n, const Shape &sh, int dev) {
   int rc;
   Allocations al;
-  std::vector<Span> vs, vd;  // the streams; the fragments
-  vs.reserve(n);
-  vd.reserve(sh.nfe);
+  std::vector<Span> frags, streams;
+  frags.reserve(sh.nfe);
+  streams.reserve(n);
   for (size_t b = 0; b < n; b++) {
     if (!has_ranges(e[b], sh.cap[b])) continue;
     if ((rc = al.check(e[b].stream, e[b].len, dev, "stream"))) return prefix_fail(rc, "entry %zu", b);
     const uintptr_t s0 = reinterpret_cast<uintptr_t>(e[b].stream);
-    vs.push_back(Span{s0, s0 + uintptr_t(e[b].len), uint32_t(b), -1});
+    streams.push_back(Span{s0, s0 + uintptr_t(e[b].len), uint32_t(b), 0u});
     for (int32_t i = 0; i < e[b].iovcnt; i++) {
       const hdfs_crc32c_iovec &f = e[b].iov[i];
       if (!f.len) continue;
       if ((rc = al.check(f.base, f.len, dev, "base"))) return prefix_fail(rc, "entry %zu: fragment %d", b, int(i));
       const uintptr_t d0 = reinterpret_cast<uintptr_t>(f.base);
-      vd.push_back(Span{d0, d0 + uintptr_t(f.len), uint32_t(b), i});
+      frags.push_back(Span{d0, d0 + uintptr_t(f.len), uint32_t(b), 1u});
     }
   }
-  // Each kind sorted by its first byte, then swept together as one merged sequence.  Fragments given in rising
-  // address order (the rows of a tensor, say) need no sort: one pass says so.
-  const auto by_lo = [](const Span &x, const Span &y) { return x.lo < y.lo; };
-  for (std::vector<Span> *v : {&vs, &vd})
-    if (!std::is_sorted(v->begin(), v->end(), by_lo)) std::sort(v->begin(), v->end(), by_lo);
-  const Span *far_d = nullptr, *far_s = nullptr;  // the fragment and the stream that reach furthest so far
-  for (size_t i = 0, j = 0; i < vs.size() || j < vd.size();) {
-    const bool dst = i >= vs.size() || (j < vd.size() && vd[j].lo < vs[i].lo);
-    const Span &c = dst ? vd[j++] : vs[i++];
-    if (far_d && c.lo < far_d->hi) return overlap_fail(*far_d, c);
-    if (dst && far_s && c.lo < far_s->hi) return overlap_fail(c, *far_s);
-    const Span *&far = dst ? far_d : far_s;
-    if (!far || c.hi > far->hi) far = &c;
-  }
-  return HDFS_CRC32C_OK;
+  // Fragments given in rising address order (the rows of a tensor, say) need no sort: one pass says so.
+  Span sw, so;
+  if (!(rc = check_overlaps(frags, streams, &sw, &so))) return rc;
+  // say which fragments: a span's is the first of its entry with that range, but for `skip`
+  const auto frag_of = [&](const Span &s, int32_t skip) {
+    for (int32_t i = 0; i < e[s.k].iovcnt; i++) {
+      const hdfs_crc32c_iovec &f = e[s.k].iov[i];
+      const uintptr_t a = reinterpret_cast<uintptr_t>(f.base);
+      if (f.len && i != skip && a == s.lo && a + uintptr_t(f.len) == s.hi) return i;
+    }
+    return skip;
+  };
+  const int32_t fw = frag_of(sw, -1);
+  if (!so.wire)
+    return fail(rc, "entry %u: fragment %d overlaps the stream of entry %u", sw.k, int(fw), so.k);
+  const int32_t fo = frag_of(so, so.k == sw.k ? fw : -1);  // one entry's fragment given twice: the other of the two
+  const bool later = sw.k > so.k || (sw.k == so.k && fw > fo);
+  return later ? fail(rc, "entry %u: fragment %d overlaps fragment %d of entry %u", sw.k, int(fw), int(fo), so.k)
+               : fail(rc, "entry %u: fragment %d overlaps fragment %d of entry %u", so.k, int(fo), int(fw), sw.k);
 }
 
 // ---- an entry handed to the main library ------------------------------------------------
-// Exactly the call of the contract.  Without a record array of the caller's the
-// walk must not be cut, so the library's own array grows until it is not.
+// Exactly the call of the contract (read_unlimited: without a record array of
+// the caller's the walk is not cut).
 int fallback(hdfs_preadv_batch_entry &x, size_t b, int proto, uint32_t chunk_size, int ctype,
              hdfs_crc32c_packet *pkts, size_t max_pkts) {
   size_t np = 0;
   uint64_t used = 0, got = 0;
-  int rc;
-  if (pkts) {
-    rc = hdfs_crc32c_read_packets(x.stream, x.len, proto, chunk_size, ctype, x.client_offset, x.read_len, x.iov,
-                                  x.iovcnt, pkts + b * max_pkts, max_pkts, &np, &used, &got);
-  } else {
-    // a complete framing-clean packet has at least 25 bytes, and one record ends the walk
-    const uint64_t most = x.len / 25u + 2u;
-    uint64_t room = most < 4096u ? most : 4096u;
-    for (;;) {
-      if (g_s.recs.size() < room) g_s.recs.resize(size_t(room));
-      rc = hdfs_crc32c_read_packets(x.stream, x.len, proto, chunk_size, ctype, x.client_offset, x.read_len, x.iov,
-                                    x.iovcnt, g_s.recs.data(), size_t(room), &np, &used, &got);
-      if (rc < 0 || np < room || room >= most) break;
-      room = room * 16u < most ? room * 16u : most;
-    }
-  }
+  const int rc = read_unlimited(g_s.recs, x.stream, x.len, proto, chunk_size, ctype, x.client_offset, x.read_len, x.iov,
+                                x.iovcnt, pkts ? pkts + b * max_pkts : nullptr, max_pkts, &np, &used, &got);
   x.rc = rc;
   x.path = HDFS_PREADV_BATCH_PATH_FALLBACK;
   if (rc < 0) return engine_fail(rc, "read_packets"), prefix_fail(rc, "entry %zu", b);
@@ -256,8 +216,7 @@ int read_windows(hdfs_preadv_batch_entry *e, size_t n, int proto, uint32_t chunk
   int rc = check_arguments(e, n, proto, chunk_size, ctype, sh);
   if (rc) return rc;
   if (timing) {  // decided by the arguments alone, before any device is asked
-    if (iters < 1 || !ms_per_iter) return fail(HDFS_CRC32C_EINVAL, "iters >= 1 and ms_per_iter are needed");
-    if ((rc = Fused::flags_ok(flags))) return rc;
+    if ((rc = timing_args_ok(iters, ms_per_iter)) || (rc = Fused::flags_ok(flags))) return rc;
   }
   int dev = -1;
   if ((rc = engine_device(&dev))) return rc;
@@ -279,36 +238,19 @@ int read_windows(hdfs_preadv_batch_entry *e, size_t n, int proto, uint32_t chunk
     return le;
   };
   const size_t back = T.base + T.p.desc;  // what the probe writes starts here
-  hipError_t he = hipMemcpyAsync(dv, pin, T.up, hipMemcpyHostToDevice, st);
-  if (he == hipSuccess) he = launches();
-  if (he == hipSuccess) he = hipMemcpyAsync(pin + back, dv + back, T.bytes - back, hipMemcpyDeviceToHost, st);
-  if (he == hipSuccess && timing) {
-    he = hipEventRecord(g_s.ev[0], st);
-    for (int i = 0; i < iters && he == hipSuccess; i++) he = launches();
-    if (he == hipSuccess) he = hipEventRecord(g_s.ev[1], st);
-  }
-  // always synchronised, even after an error: the tables are out of the device's use before the lock goes
-  const hipError_t se = hipStreamSynchronize(st);
-  if (he == hipSuccess) he = se;
-  if (he != hipSuccess) return fail(HDFS_CRC32C_EHIP, "preadv batch: %s", hipGetErrorString(he));
-  if (timing) {
-    float ms = 0;
-    if ((he = hipEventElapsedTime(&ms, g_s.ev[0], g_s.ev[1])) != hipSuccess)
-      return fail(HDFS_CRC32C_EHIP, "preadv batch: %s", hipGetErrorString(he));
-    *ms_per_iter = double(ms) / iters;
-  }
+  if ((rc = probed_run(st, g_s.tab, 0, T.up, back, T.bytes, g_s.ev, timing ? iters : 0, ms_per_iter, "preadv batch",
+                       launches)))
+    return rc;
   const uint8_t *pb = pin + T.base;
   const Window *desc = reinterpret_cast<const Window *>(pb + T.p.desc);
   const uint32_t *slot = reinterpret_cast<const uint32_t *>(pb + T.p.slot);
   const uint32_t *status = reinterpret_cast<const uint32_t *>(pb + T.p.status);
   const uint32_t nreg = reinterpret_cast<const uint32_t *>(pb + T.p.meta)[0];
-  int first_neg = 0, first_pos = 0;
-  char neg_text[sizeof(g_err)] = "";
+  Outcomes out;
   for (size_t b = 0; b < n; b++) {
     hdfs_preadv_batch_entry &x = e[b];
     const uint32_t s = slot[b];
-    if (s != kNoSlot && (s >= nreg || desc[s].d.entry != b))
-      return fail(HDFS_CRC32C_EHIP, "internal: the probe's tables do not add up at entry %zu", b);
+    if (!slot_adds_up(s, kNoSlot, nreg, b, [&](uint32_t i) { return desc[i].d.entry; })) return tables_fail(b);
     if (s != kNoSlot && !status[s]) {
       const Desc &d = desc[s].d;
       x.rc = 0;
@@ -320,18 +262,9 @@ int read_windows(hdfs_preadv_batch_entry *e, size_t n, int proto, uint32_t chunk
         for (uint32_t i = 0; i < d.npk; i++) pkts[b * max_pkts + i] = record_of(packet_of(d, i));
       continue;
     }
-    const int r = fallback(x, b, proto, chunk_size, ctype, pkts, max_pkts);
-    if (r < 0 && !first_neg) {
-      first_neg = r;
-      std::memcpy(neg_text, g_err, sizeof(neg_text));
-    }
-    if (r > 0 && !first_pos) first_pos = r;
+    out.note(fallback(x, b, proto, chunk_size, ctype, pkts, max_pkts));
   }
-  if (first_neg) {
-    std::memcpy(g_err, neg_text, sizeof(neg_text));
-    return first_neg;
-  }
-  return first_pos;
+  return out.result();
 }
 
 }  // namespace

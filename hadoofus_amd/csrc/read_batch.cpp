@@ -8,7 +8,9 @@
 // (wire_fused_host.h, built out of crc32c_tables.h).  Every other entry is
 // hdfs_crc32c_read_packets' work, called here after the synchronise: this
 // file holds no walk of its own.  The records of a regular entry follow from
-// its descriptor (read_batch_layout.h: packet_of, record_of).
+// its descriptor (read_batch_layout.h: packet_of, record_of).  The run, the
+// collection of the entries' outcomes and the scratch are read_batch_host.h's,
+// the overlap sweep companion_support.h's.
 #include <hip/hip_runtime.h>
 
 #include <mutex>
@@ -16,6 +18,7 @@
 
 #include "companion_support.h"
 #include "hadoofus_read_batch.h"
+#include "read_batch_host.h"
 #include "read_batch_internal.h"
 #include "read_batch_layout.h"
 #include "wire_fused_host.h"
@@ -37,20 +40,7 @@ static_assert(HDFS_READ_BATCH_MAX_ENTRIES == kMaxEntries, "the header's limit is
 // kernels or under the host's reading of them.
 std::mutex g_mu;
 using Fused = hdfs_wire_fused::DeviceState<prepare_unframe_fused_batch, kBatchMaxGroups>;
-struct Scratch : DeviceScratch {
-  Fused fused;
-  TablePair tab;
-  std::vector<hdfs_crc32c_packet> recs;  // a fallback entry's records when the caller wants none
-
-  int reserve(int to, size_t tab_bytes) {
-    int rc = bind(to, "stream", [this] {
-      fused.release();
-      tab.release();
-    });
-    if (rc || (rc = fused.setup(to))) return rc;
-    return tab.reserve(tab_bytes, kTableFloor);
-  }
-} g_s;
+ReadScratch<Fused> g_s;
 
 void clear_outputs(hdfs_read_batch_entry *e, size_t n) {
   for (size_t b = 0; b < n; b++) {
@@ -87,51 +77,30 @@ bool has_ranges(const hdfs_read_batch_entry &x) { return x.len && x.dst_cap; }
 int check_batch_places(const hdfs_read_batch_entry *e, size_t n, int dev) {
   int rc;
   Allocations al;
+  std::vector<Span> dsts, streams;
+  dsts.reserve(n);
+  streams.reserve(n);
   for (size_t b = 0; b < n; b++) {
     if (!has_ranges(e[b])) continue;
     if ((rc = al.check(e[b].stream, e[b].len, dev, "stream")) || (rc = al.check(e[b].dst, e[b].dst_cap, dev, "dst")))
       return prefix_fail(rc, "entry %zu", b);
+    const uintptr_t s0 = reinterpret_cast<uintptr_t>(e[b].stream), d0 = reinterpret_cast<uintptr_t>(e[b].dst);
+    streams.push_back(Span{s0, s0 + uintptr_t(e[b].len), uint32_t(b), 0u});
+    dsts.push_back(Span{d0, d0 + uintptr_t(e[b].dst_cap), uint32_t(b), 1u});
   }
-  for (size_t b = 0; b < n; b++) {
-    if (!has_ranges(e[b])) continue;
-    const uintptr_t d0 = reinterpret_cast<uintptr_t>(e[b].dst), d1 = d0 + uintptr_t(e[b].dst_cap);
-    for (size_t o = 0; o < n; o++) {
-      if (!has_ranges(e[o])) continue;
-      const uintptr_t s0 = reinterpret_cast<uintptr_t>(e[o].stream), s1 = s0 + uintptr_t(e[o].len);
-      if (s0 < d1 && d0 < s1)
-        return fail(HDFS_CRC32C_EINVAL, "entry %zu: dst overlaps the stream of entry %zu", b, o);
-      const uintptr_t o0 = reinterpret_cast<uintptr_t>(e[o].dst), o1 = o0 + uintptr_t(e[o].dst_cap);
-      if (o > b && o0 < d1 && d0 < o1)
-        return fail(HDFS_CRC32C_EINVAL, "entry %zu: dst overlaps the dst of entry %zu", o, b);
-    }
-  }
-  return HDFS_CRC32C_OK;
+  return check_overlaps(dsts, streams, nullptr, nullptr, SpanNouns{"dst", "stream"});
 }
 
 // ---- an entry handed to the main library ------------------------------------------------
-// Exactly the call of the contract.  Without a record array of the caller's the
-// walk must not be cut, so the library's own array grows until it is not.
+// Exactly the call of the contract (read_unlimited: without a record array of
+// the caller's the walk is not cut).
 int fallback(hdfs_read_batch_entry &x, size_t b, int proto, uint32_t chunk_size, int ctype, hdfs_crc32c_packet *pkts,
              size_t max_pkts) {
   const hdfs_crc32c_iovec iov{x.dst, x.dst_cap};
   size_t np = 0;
   uint64_t used = 0, got = 0;
-  int rc;
-  if (pkts) {
-    rc = hdfs_crc32c_read_packets(x.stream, x.len, proto, chunk_size, ctype, 0, HDFS_CRC32C_READ_ALL, &iov, 1,
-                                  pkts + b * max_pkts, max_pkts, &np, &used, &got);
-  } else {
-    // a complete framing-clean packet has at least 25 bytes, and one record ends the walk
-    const uint64_t most = x.len / 25u + 2u;
-    uint64_t room = most < 4096u ? most : 4096u;
-    for (;;) {
-      if (g_s.recs.size() < room) g_s.recs.resize(size_t(room));
-      rc = hdfs_crc32c_read_packets(x.stream, x.len, proto, chunk_size, ctype, 0, HDFS_CRC32C_READ_ALL, &iov, 1,
-                                    g_s.recs.data(), size_t(room), &np, &used, &got);
-      if (rc < 0 || np < room || room >= most) break;
-      room = room * 16u < most ? room * 16u : most;
-    }
-  }
+  const int rc = read_unlimited(g_s.recs, x.stream, x.len, proto, chunk_size, ctype, 0, HDFS_CRC32C_READ_ALL, &iov, 1,
+                                pkts ? pkts + b * max_pkts : nullptr, max_pkts, &np, &used, &got);
   x.rc = rc;
   x.path = HDFS_READ_BATCH_PATH_FALLBACK;
   if (rc < 0) return engine_fail(rc, "read_packets"), prefix_fail(rc, "entry %zu", b);
@@ -151,8 +120,7 @@ int read_blocks(hdfs_read_batch_entry *e, size_t n, int proto, uint32_t chunk_si
   int rc = check_arguments(e, n, proto, chunk_size, ctype);
   if (rc) return rc;
   if (timing) {  // decided by the arguments alone, before any device is asked
-    if (iters < 1 || !ms_per_iter) return fail(HDFS_CRC32C_EINVAL, "iters >= 1 and ms_per_iter are needed");
-    if ((rc = Fused::flags_ok(flags))) return rc;
+    if ((rc = timing_args_ok(iters, ms_per_iter)) || (rc = Fused::flags_ok(flags))) return rc;
   }
   int dev = -1;
   if ((rc = engine_device(&dev))) return rc;
@@ -176,36 +144,18 @@ int read_blocks(hdfs_read_batch_entry *e, size_t n, int proto, uint32_t chunk_si
     if (le == hipSuccess) le = launch_unframe_fused_batch(dv, uint32_t(n), uint32_t(proto), crc_tab, groups, st);
     return le;
   };
-  hipError_t he = hipMemcpyAsync(dv + T.in, pin + T.in, n * sizeof(Entry), hipMemcpyHostToDevice, st);
-  if (he == hipSuccess) he = launches();
-  if (he == hipSuccess)
-    he = hipMemcpyAsync(pin + T.desc, dv + T.desc, T.bytes - T.desc, hipMemcpyDeviceToHost, st);
-  if (he == hipSuccess && timing) {
-    he = hipEventRecord(g_s.ev[0], st);
-    for (int i = 0; i < iters && he == hipSuccess; i++) he = launches();
-    if (he == hipSuccess) he = hipEventRecord(g_s.ev[1], st);
-  }
-  // always synchronised, even after an error: the tables are out of the device's use before the lock goes
-  const hipError_t se = hipStreamSynchronize(st);
-  if (he == hipSuccess) he = se;
-  if (he != hipSuccess) return fail(HDFS_CRC32C_EHIP, "read batch: %s", hipGetErrorString(he));
-  if (timing) {
-    float ms = 0;
-    if ((he = hipEventElapsedTime(&ms, g_s.ev[0], g_s.ev[1])) != hipSuccess)
-      return fail(HDFS_CRC32C_EHIP, "read batch: %s", hipGetErrorString(he));
-    *ms_per_iter = double(ms) / iters;
-  }
+  if ((rc = probed_run(st, g_s.tab, T.in, n * sizeof(Entry), T.desc, T.bytes, g_s.ev, timing ? iters : 0, ms_per_iter,
+                       "read batch", launches)))
+    return rc;
   const Desc *desc = reinterpret_cast<const Desc *>(pin + T.desc);
   const uint32_t *slot = reinterpret_cast<const uint32_t *>(pin + T.slot);
   const uint32_t *status = reinterpret_cast<const uint32_t *>(pin + T.status);
   const uint32_t nreg = reinterpret_cast<const uint32_t *>(pin + T.meta)[0];
-  int first_neg = 0, first_pos = 0;
-  char neg_text[sizeof(g_err)] = "";
+  Outcomes out;
   for (size_t b = 0; b < n; b++) {
     hdfs_read_batch_entry &x = e[b];
     const uint32_t s = slot[b];
-    if (s != kNoSlot && (s >= nreg || desc[s].entry != b))
-      return fail(HDFS_CRC32C_EHIP, "internal: the probe's tables do not add up at entry %zu", b);
+    if (!slot_adds_up(s, kNoSlot, nreg, b, [&](uint32_t i) { return desc[i].entry; })) return tables_fail(b);
     if (s != kNoSlot && !status[s]) {
       const Desc &d = desc[s];
       x.rc = 0;
@@ -217,18 +167,9 @@ int read_blocks(hdfs_read_batch_entry *e, size_t n, int proto, uint32_t chunk_si
         for (uint32_t i = 0; i < d.npk; i++) pkts[b * max_pkts + i] = record_of(packet_of(d, i));
       continue;
     }
-    const int r = fallback(x, b, proto, chunk_size, ctype, pkts, max_pkts);
-    if (r < 0 && !first_neg) {
-      first_neg = r;
-      std::memcpy(neg_text, g_err, sizeof(neg_text));
-    }
-    if (r > 0 && !first_pos) first_pos = r;
+    out.note(fallback(x, b, proto, chunk_size, ctype, pkts, max_pkts));
   }
-  if (first_neg) {
-    std::memcpy(g_err, neg_text, sizeof(neg_text));
-    return first_neg;
-  }
-  return first_pos;
+  return out.result();
 }
 
 }  // namespace

@@ -10,7 +10,9 @@
 // the library's scratch buffer, then the fused batch write library's kernel
 // (wire_fused_batch_kernels.hip, compiled into this library as it stands) over
 // a table of that one write, laid out by wire_layout.h.  This file holds no
-// walk and no framing of its own.
+// walk and no framing of its own.  The run, the collection of the entries'
+// outcomes and the base of the scratch are read_batch_host.h's, the overlap
+// sweep companion_support.h's.
 #include <hip/hip_runtime.h>
 
 #include <mutex>
@@ -18,6 +20,7 @@
 
 #include "companion_support.h"
 #include "hadoofus_relay_batch.h"
+#include "read_batch_host.h"
 #include "read_batch_layout.h"
 #include "relay_batch_internal.h"
 #include "relay_batch_lookup.h"
@@ -50,21 +53,15 @@ hipError_t prepare_both() {
 // upload to the last fallback entry.
 std::mutex g_mu;
 using Fused = hdfs_wire_fused::DeviceState<prepare_both, kBatchMaxGroups>;
-struct Scratch : DeviceScratch {
-  Fused fused;
-  TablePair tab, one;
+struct Scratch : ReadScratch<Fused> {
+  TablePair one;
   DeviceBuffer payload;
-  std::vector<hdfs_crc32c_packet> recs;  // a fallback entry's records
 
   int reserve(int to, size_t tab_bytes) {
-    int rc = bind(to, "stream", [this] {
-      fused.release();
-      tab.release();
+    return ReadScratch::reserve(to, tab_bytes, [this] {
       one.release();
       payload.release();
     });
-    if (rc || (rc = fused.setup(to))) return rc;
-    return tab.reserve(tab_bytes, kTableFloor);
   }
 } g_s;
 
@@ -103,24 +100,18 @@ int check_arguments(hdfs_relay_batch_entry *e, size_t n, int proto, uint32_t chu
 int check_batch_places(const hdfs_relay_batch_entry *e, size_t n, int dev) {
   int rc;
   Allocations al;
+  std::vector<Span> wires, streams;
+  wires.reserve(n);
+  streams.reserve(n);
   for (size_t b = 0; b < n; b++) {
     if ((e[b].len && (rc = al.check(e[b].stream, e[b].len, dev, "stream"))) ||
         (e[b].wire_cap && (rc = al.check(e[b].wire, e[b].wire_cap, dev, "wire"))))
       return prefix_fail(rc, "entry %zu", b);
+    const uintptr_t s0 = reinterpret_cast<uintptr_t>(e[b].stream), w0 = reinterpret_cast<uintptr_t>(e[b].wire);
+    if (e[b].len) streams.push_back(Span{s0, s0 + uintptr_t(e[b].len), uint32_t(b), 0u});
+    if (e[b].wire_cap) wires.push_back(Span{w0, w0 + uintptr_t(e[b].wire_cap), uint32_t(b), 1u});
   }
-  for (size_t b = 0; b < n; b++) {
-    if (!e[b].wire_cap) continue;
-    const uintptr_t d0 = reinterpret_cast<uintptr_t>(e[b].wire), d1 = d0 + uintptr_t(e[b].wire_cap);
-    for (size_t o = 0; o < n; o++) {
-      const uintptr_t s0 = reinterpret_cast<uintptr_t>(e[o].stream), s1 = s0 + uintptr_t(e[o].len);
-      if (e[o].len && s0 < d1 && d0 < s1)
-        return fail(HDFS_CRC32C_EINVAL, "entry %zu: wire overlaps the stream of entry %zu", b, o);
-      const uintptr_t o0 = reinterpret_cast<uintptr_t>(e[o].wire), o1 = o0 + uintptr_t(e[o].wire_cap);
-      if (o > b && e[o].wire_cap && o0 < d1 && d0 < o1)
-        return fail(HDFS_CRC32C_EINVAL, "entry %zu: wire overlaps the wire of entry %zu", o, b);
-    }
-  }
-  return HDFS_CRC32C_OK;
+  return check_overlaps(wires, streams, nullptr, nullptr, SpanNouns{"wire", "stream"});
 }
 
 // ---- the layout of a write ---------------------------------------------------------------
@@ -141,8 +132,8 @@ int layout_write(uint64_t payload, int64_t off, int64_t seq, int proto, int ctyp
 
 // ---- an entry served after the synchronise --------------------------------------------------
 // The read: exactly the call of the contract, into the library's buffer (the
-// payload is shorter than the stream).  The walk must not be cut, so the record
-// array grows until it is not.  Then, where the read is clean and the stream
+// payload is shorter than the stream), the walk not cut (read_unlimited).
+// Then, where the read is clean and the stream
 // fits, the write: frame_fused_batch_kernel over a table of this one write.
 int fallback(hdfs_relay_batch_entry &x, size_t b, int proto, uint32_t chunk_size, int ctype, hipStream_t st) {
   x.path = HDFS_RELAY_BATCH_PATH_FALLBACK;
@@ -151,16 +142,8 @@ int fallback(hdfs_relay_batch_entry &x, size_t b, int proto, uint32_t chunk_size
   const hdfs_crc32c_iovec iov{g_s.payload.p, x.len};
   size_t np = 0;
   uint64_t used = 0, got = 0;
-  // a complete framing-clean packet has at least 25 bytes, and one record ends the walk
-  const uint64_t most = x.len / 25u + 2u;
-  uint64_t room = most < 4096u ? most : 4096u;
-  for (;;) {
-    if (g_s.recs.size() < room) g_s.recs.resize(size_t(room));
-    rc = hdfs_crc32c_read_packets(x.stream, x.len, proto, chunk_size, ctype, 0, HDFS_CRC32C_READ_ALL, &iov, 1,
-                                  g_s.recs.data(), size_t(room), &np, &used, &got);
-    if (rc < 0 || np < room || room >= most) break;
-    room = room * 16u < most ? room * 16u : most;
-  }
+  rc = read_unlimited(g_s.recs, x.stream, x.len, proto, chunk_size, ctype, 0, HDFS_CRC32C_READ_ALL, &iov, 1, nullptr, 0,
+                      &np, &used, &got);
   x.rc = rc;
   if (rc < 0) return engine_fail(rc, "read_packets"), prefix_fail(rc, "entry %zu", b);
   x.consumed = used;
@@ -208,8 +191,7 @@ int relay(hdfs_relay_batch_entry *e, size_t n, int proto, uint32_t chunk_size, i
   int rc = check_arguments(e, n, proto, chunk_size, ctype);
   if (rc) return rc;
   if (timing) {  // decided by the arguments alone, before any device is asked
-    if (iters < 1 || !ms_per_iter) return fail(HDFS_CRC32C_EINVAL, "iters >= 1 and ms_per_iter are needed");
-    if ((rc = Fused::flags_ok(flags))) return rc;
+    if ((rc = timing_args_ok(iters, ms_per_iter)) || (rc = Fused::flags_ok(flags))) return rc;
   }
   int dev = -1;
   if ((rc = engine_device(&dev))) return rc;
@@ -239,37 +221,20 @@ int relay(hdfs_relay_batch_entry *e, size_t n, int proto, uint32_t chunk_size, i
     if (le == hipSuccess) le = launch_relay_fused_batch(dv, uint32_t(n), uint32_t(proto), crc_tab, groups, st);
     return le;
   };
-  hipError_t he = hipMemcpyAsync(dv + T.in, pin + T.in, n * sizeof(Entry), hipMemcpyHostToDevice, st);
-  if (he == hipSuccess) he = launches();
-  if (he == hipSuccess)
-    he = hipMemcpyAsync(pin + T.desc, dv + T.desc, T.bytes - T.desc, hipMemcpyDeviceToHost, st);
-  if (he == hipSuccess && timing) {
-    he = hipEventRecord(g_s.ev[0], st);
-    for (int i = 0; i < iters && he == hipSuccess; i++) he = launches();
-    if (he == hipSuccess) he = hipEventRecord(g_s.ev[1], st);
-  }
-  // always synchronised, even after an error: the tables are out of the device's use before the lock goes
-  const hipError_t se = hipStreamSynchronize(st);
-  if (he == hipSuccess) he = se;
-  if (he != hipSuccess) return fail(HDFS_CRC32C_EHIP, "relay batch: %s", hipGetErrorString(he));
-  if (timing) {
-    float ms = 0;
-    if ((he = hipEventElapsedTime(&ms, g_s.ev[0], g_s.ev[1])) != hipSuccess)
-      return fail(HDFS_CRC32C_EHIP, "relay batch: %s", hipGetErrorString(he));
-    *ms_per_iter = double(ms) / iters;
-  }
+  if ((rc = probed_run(st, g_s.tab, T.in, n * sizeof(Entry), T.desc, T.bytes, g_s.ev, timing ? iters : 0, ms_per_iter,
+                       "relay batch", launches)))
+    return rc;
   const Desc *desc = reinterpret_cast<const Desc *>(pin + T.desc);
   const uint32_t *slot = reinterpret_cast<const uint32_t *>(pin + T.slot);
   const uint32_t *status = reinterpret_cast<const uint32_t *>(pin + T.status);
   const uint32_t nreg = reinterpret_cast<const uint32_t *>(pin + T.meta)[0];
-  int first_neg = 0, first_pos = 0;
-  char neg_text[sizeof(g_err)] = "";
+  Outcomes out;
   for (size_t b = 0; b < n; b++) {
     hdfs_relay_batch_entry &x = e[b];
     const uint32_t s = slot[b];
-    if (s != kNoSlot && (s >= nreg || desc[s].in.entry != b || in_packets(desc[s].g) != desc[s].in.npk ||
-                         desc[s].wire_len > x.wire_cap))
-      return fail(HDFS_CRC32C_EHIP, "internal: the probe's tables do not add up at entry %zu", b);
+    if (!slot_adds_up(s, kNoSlot, nreg, b, [&](uint32_t i) { return desc[i].in.entry; }) ||
+        (s != kNoSlot && (in_packets(desc[s].g) != desc[s].in.npk || desc[s].wire_len > x.wire_cap)))
+      return tables_fail(b);
     if (s != kNoSlot && !status[s]) {
       const Desc &d = desc[s];
       x.rc = 0;
@@ -281,18 +246,9 @@ int relay(hdfs_relay_batch_entry *e, size_t n, int proto, uint32_t chunk_size, i
       x.npkts = d.npk;
       continue;
     }
-    const int r = fallback(x, b, proto, chunk_size, ctype, st);
-    if (r < 0 && !first_neg) {
-      first_neg = r;
-      std::memcpy(neg_text, g_err, sizeof(neg_text));
-    }
-    if (r > 0 && !first_pos) first_pos = r;
+    out.note(fallback(x, b, proto, chunk_size, ctype, st));
   }
-  if (first_neg) {
-    std::memcpy(g_err, neg_text, sizeof(neg_text));
-    return first_neg;
-  }
-  return first_pos;
+  return out.result();
 }
 
 }  // namespace

@@ -151,47 +151,12 @@ int check_entries(const Entry *w, size_t n, size_t with_wire, const Batch &B, co
 }
 
 // ---- where the buffers live -------------------------------------------------------
-// No wire range overlaps another wire range or a data range: the intervals
-// sorted by their first byte, then one pass that remembers the furthest end
-// among the wire ranges and among the data ranges seen so far.
-struct Span {
-  uintptr_t lo, hi;  // [lo, hi), not empty
-  uint32_t k;        // entry
-  uint32_t wire;     // 1: a wire range
-};
-
-// The sweep's order; a caller with very many spans may hand them over in it.
-inline bool span_before(const Span &a, const Span &b) {
-  return a.lo != b.lo ? a.lo < b.lo : (a.wire != b.wire ? a.wire > b.wire : a.k < b.k);
-}
-
-// hit_wire / hit_other (may be NULL): on a refusal, the wire range and the
-// range it overlaps, for a caller whose data ranges are more than one per
-// entry and who names the one at fault.
-inline int check_overlaps(std::vector<Span> &v, Span *hit_wire = nullptr, Span *hit_other = nullptr) {
-  if (!std::is_sorted(v.begin(), v.end(), span_before)) std::sort(v.begin(), v.end(), span_before);
-  const auto hit = [&](const Span &wire, const Span &other) {
-    if (hit_wire) *hit_wire = wire;
-    if (hit_other) *hit_other = other;
-  };
-  const Span *far_w = nullptr, *far_d = nullptr;
-  for (const Span &s : v) {
-    // every span ahead of s starts at or below s.lo: it overlaps s iff it ends behind s.lo
-    if (far_w && far_w->hi > s.lo) {
-      const uint32_t a = std::max(far_w->k, s.k), b = std::min(far_w->k, s.k);
-      hit(*far_w, s);
-      return s.wire ? fail(HDFS_CRC32C_EINVAL, "entry %u: wire overlaps the wire of entry %u", a, b)
-                    : fail(HDFS_CRC32C_EINVAL, "entry %u: wire overlaps the data of entry %u", far_w->k, s.k);
-    }
-    if (s.wire && far_d && far_d->hi > s.lo) {
-      hit(s, *far_d);
-      return fail(HDFS_CRC32C_EINVAL, "entry %u: wire overlaps the data of entry %u", s.k, far_d->k);
-    }
-    const Span *&far = s.wire ? far_w : far_d;
-    if (!far || s.hi > far->hi) far = &s;
-  }
-  return HDFS_CRC32C_OK;
-}
+// No wire range overlaps another wire range or a data range: the sweep of the
+// companions' shared host support (hdfs_companion::check_overlaps, which the
+// read-side libraries call too), with its default nouns "wire" and "data".
+using hdfs_companion::check_overlaps;
+using hdfs_companion::Span;
+using hdfs_companion::span_before;
 
 // Every entry's data and stream inside one allocation of device `dev` each,
 // and no stream over another stream or over any data.

@@ -58,8 +58,9 @@
  *            2 MiB stream (its middle), 30000      0.39 (0.39-0.46)   27.2 (27.1-27.3)      1.15 (1.13-1.25)    0.23
  * This call's range is clear of the loop's in all five rows (1.2 times for
  * 128 MiB reads, 42 to 178 times for small ones).  Against the read batch's
- * READ_ALL call: 4 times faster for 1 024 reads of 4 KiB (that call compares
- * every pair of entries for overlaps, this one sorts them) and 2.9 times where
+ * READ_ALL call: 4 times faster for 1 024 reads of 4 KiB (in that run that call
+ * compared every pair of entries for overlaps and this one sorted them; since
+ * then both call the one sweep of companion_support.h, see below) and 2.9 times where
  * the stream is taken from the middle of a longer one and the read ends early
  * (the last row: 2 packets taken of 21, READ_ALL walks and delivers the whole
  * stream); the ranges OVERLAP in the other three rows, and at 1 MiB this
@@ -68,6 +69,9 @@
  * step, so streams of tiny packets cost a step each.  Not measured: CRC32, v1,
  * a caller's stream, fallbacks in the batch, many reads of one shared stream, a
  * second run of the command.
+ * Since the read batch calls the shared sweep too, a later run of the same
+ * command (--quick) gave for 1 024 x 4 KiB: this call 0.188 (0.185-0.202), the
+ * READ_ALL batch 0.214 (0.208-0.232), 1.1 times apart.
  *
  * Status codes are the main library's HDFS_CRC32C_* (0 = OK, negative =
  * failure, text in hdfs_pread_batch_last_error()).

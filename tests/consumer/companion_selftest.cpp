@@ -1,7 +1,8 @@
 // CPU self-test of the companion libraries' shared host support
 // (hadoofus_amd/csrc/companion_support.h, grid_segments / timed_frame_run of
-// wire_layout.h, the fused libraries' device state of wire_fused_host.h and
-// the batch front end of wire_batch_layout.h) against a fake HIP runtime and a
+// wire_layout.h, the fused libraries' device state of wire_fused_host.h, the
+// batch front end of wire_batch_layout.h and the read side's skeleton of
+// read_batch_host.h) against a fake HIP runtime and a
 // fake engine, both defined here: the program is not linked to the HIP
 // runtime.  The fakes count and log every call, remember the current device
 // and can be told to fail, so the checks cover what the GPU tests cannot:
@@ -19,6 +20,7 @@
 #include <vector>
 
 #include "companion_support.h"
+#include "read_batch_host.h"
 #include "wire_batch_layout.h"
 #include "wire_fused_host.h"
 #include "wire_layout.h"
@@ -53,6 +55,13 @@ struct Fake {
   hipError_t sticky = hipSuccess;
   int fail_malloc = 0, fail_host_malloc = 0, fail_stream = 0, fail_sync = 0, fail_range = 0, fail_launch = 0;
   int fail_event = 0;  // n > 0: the n-th hipEventCreate from now fails
+  int fail_async = 0;  // n > 0: the n-th hipMemcpyAsync from now fails
+  struct Copy {
+    const void *dst, *src;
+    size_t n;
+    hipMemcpyKind kind;
+  };
+  std::vector<Copy> copies;  // what hipMemcpyAsync was given; nothing is copied
   int events = 0;      // live events
   int cus = 256;       // hipDeviceGetAttribute's answer
   size_t copied = 0;   // bytes of the last hipMemcpy
@@ -61,6 +70,33 @@ struct Fake {
   // the fake engine
   int init_rc = 0, bound_rc = 0, exec_rc = 0, engine_dev = 0, plans_destroyed = 0;
   std::string engine_text = "engine text";
+  // hdfs_crc32c_read_packets: a stream of read_records records, as many written as there is room for
+  struct Read {
+    const void *stream;
+    uint64_t len;
+    int64_t client_offset, read_len;
+    const hdfs_crc32c_iovec *iov;
+    int iovcnt;
+    hdfs_crc32c_packet *pkts;
+    size_t room;
+  };
+  std::vector<Read> reads;
+  size_t read_records = 0;
+  int read_rc = 0;
+  // hdfs_crc32c_parse_packets: one scripted piece per call
+  struct Piece {
+    int rc;
+    size_t np;
+    uint64_t used;
+    bool ends;  // its last record is the empty last packet
+  };
+  struct Parse {
+    const void *stream;
+    uint64_t len;
+    size_t room;
+  };
+  std::vector<Piece> pieces;
+  std::vector<Parse> parses;
 
   void called(const char *name) {
     calls++;
@@ -218,6 +254,11 @@ hipError_t hipMemcpy(void *dst, const void *src, size_t n, hipMemcpyKind) {
   F.copied = n;
   return hipSuccess;
 }
+hipError_t hipMemcpyAsync(void *dst, const void *src, size_t n, hipMemcpyKind kind, hipStream_t) {
+  F.called("hipMemcpyAsync");
+  F.copies.push_back(Fake::Copy{dst, src, n, kind});
+  return F.fail_async && !--F.fail_async ? F.failed(hipErrorOutOfMemory) : hipSuccess;
+}
 hipError_t hipDeviceGetAttribute(int *v, hipDeviceAttribute_t, int) {
   F.called("hipDeviceGetAttribute");
   *v = F.cus;
@@ -247,6 +288,39 @@ const char *hdfs_crc32c_last_error(void) { return F.engine_text.c_str(); }
 int hdfs_crc32c_plan_execute(hdfs_crc32c_plan *, void *) {
   F.called("plan_execute");
   return F.exec_rc;
+}
+int hdfs_crc32c_read_packets(const void *stream, uint64_t len, int, uint32_t, int, int64_t client_offset, int64_t read_len,
+                             const hdfs_crc32c_iovec *iov, int iovcnt, hdfs_crc32c_packet *pkts, size_t max_pkts,
+                             size_t *npkts, uint64_t *consumed, uint64_t *delivered) {
+  F.called("read_packets");
+  F.reads.push_back(Fake::Read{stream, len, client_offset, read_len, iov, iovcnt, pkts, max_pkts});
+  if (F.read_rc < 0) return F.read_rc;
+  *npkts = std::min(max_pkts, F.read_records);
+  for (size_t i = 0; i < *npkts; i++) pkts[i].offset_in_block = int64_t(1000 + i);  // the room is really there
+  *consumed = len;
+  *delivered = 77;
+  return F.read_rc;
+}
+int hdfs_crc32c_parse_packets(const void *stream, uint64_t len, int, uint32_t, int, hdfs_crc32c_packet *pkts,
+                              size_t max_pkts, size_t *npkts, uint64_t *consumed) {
+  F.called("parse_packets");
+  const Fake::Piece p = F.pieces.at(F.parses.size());
+  F.parses.push_back(Fake::Parse{stream, len, max_pkts});
+  if (p.rc < 0) return p.rc;
+  if (p.np > max_pkts) std::abort();
+  for (size_t i = 0; i < p.np; i++) {
+    pkts[i] = hdfs_crc32c_packet{};
+    pkts[i].stream_off = 100 * i;
+    pkts[i].offset_in_block = int64_t(4096 + len);  // another one in every piece
+    pkts[i].data_len = 10;
+    pkts[i].crc_len = 4;
+    pkts[i].header_len = 31;
+  }
+  if (p.np && p.rc > 0) pkts[p.np - 1].error = p.rc;
+  if (p.np && p.ends) pkts[p.np - 1].data_len = pkts[p.np - 1].crc_len = 0;
+  *npkts = p.np;
+  *consumed = p.used;
+  return p.rc;
 }
 void hdfs_crc32c_plan_destroy(hdfs_crc32c_plan *) {
   F.called("plan_destroy");
@@ -716,7 +790,10 @@ void test_placement() {
 }
 
 // ---- a batch: no stream over another stream or over any data -----------------------------------------
-using hdfs_wire::Span;
+using hdfs_wire::Span;  // companion_support.h's, through the using declaration of wire_batch_layout.h
+
+// The nouns the libraries give the sweep: the wire side's defaults, and the read batches'.
+const SpanNouns kNouns[2] = {SpanNouns{}, SpanNouns{"dst", "stream"}};
 
 bool meet(const Span &a, const Span &b) { return a.lo < b.hi && b.lo < a.hi; }
 
@@ -728,13 +805,14 @@ bool scan_finds_overlap(const std::vector<Span> &v) {
   return false;
 }
 
-// "entry A: wire overlaps the wire|data of entry B" names spans of v that do overlap.
-bool refusal_names_a_pair(const std::vector<Span> &v) {
+// "entry A: <writer> overlaps the <writer|reader> of entry B" names spans of v that do overlap.
+bool refusal_names_a_pair(const std::vector<Span> &v, const SpanNouns &nouns) {
   unsigned a = 0, b = 0;
-  char kind[8] = "";
-  if (std::sscanf(last_error(), "entry %u: wire overlaps the %4s of entry %u", &a, kind, &b) != 3) return false;
-  const bool other_wire = !std::strcmp(kind, "wire");
-  if (!other_wire && std::strcmp(kind, "data")) return false;
+  char first[8] = "", kind[8] = "";
+  if (std::sscanf(last_error(), "entry %u: %7s overlaps the %7s of entry %u", &a, first, kind, &b) != 4) return false;
+  if (std::strcmp(first, nouns.writer)) return false;
+  const bool other_wire = !std::strcmp(kind, nouns.writer);
+  if (!other_wire && std::strcmp(kind, nouns.reader)) return false;
   if (other_wire && a <= b) return false;  // the later entry is the one refused
   for (const Span &x : v)
     for (const Span &y : v)
@@ -745,11 +823,20 @@ bool refusal_names_a_pair(const std::vector<Span> &v) {
 // The sweep sorts its argument; the scan sees the caller's order.
 int g_refused = 0, g_allowed = 0;
 void overlaps_agree(const std::vector<Span> &v) {
-  std::vector<Span> sorted = v;
-  const int rc = hdfs_wire::check_overlaps(sorted);
   const bool bad = scan_finds_overlap(v);
   (bad ? g_refused : g_allowed)++;
-  if (rc != (bad ? HDFS_CRC32C_EINVAL : 0) || (bad && !refusal_names_a_pair(v))) {
+  for (const SpanNouns &nouns : kNouns) {
+    std::vector<Span> sorted = v;
+    const int rc = hdfs_wire::check_overlaps(sorted, nullptr, nullptr, nouns);
+    const std::string text = rc ? last_error() : "";
+    // the written and the read ranges handed over apart, in the caller's order: the same verdict, the same text
+    std::vector<Span> writers, readers;
+    for (const Span &s : v) (s.wire ? writers : readers).push_back(s);
+    Span sw{}, so{};
+    const int rc2 = check_overlaps(writers, readers, &sw, &so, nouns);
+    const bool same = rc2 == rc && (!rc || (text == last_error() && sw.wire && meet(sw, so)));
+    if (same && rc == (bad ? HDFS_CRC32C_EINVAL : 0) && (!bad || refusal_names_a_pair(v, nouns))) continue;
+    if (!same) std::printf("  apart: rc %d, text \"%s\"\n", rc2, rc2 ? last_error() : "");
     std::printf("  spans:");
     for (const Span &s : v)
       std::printf(" %s%u[%llu,%llu)", s.wire ? "w" : "d", s.k, (unsigned long long)s.lo, (unsigned long long)s.hi);
@@ -758,13 +845,28 @@ void overlaps_agree(const std::vector<Span> &v) {
   }
 }
 
+// A wire-side text with the read batches' nouns.
+std::string with_nouns(std::string text, const SpanNouns &nouns) {
+  for (const char *old : {"wire", "data"}) {
+    const std::string now = old[0] == 'w' ? nouns.writer : nouns.reader;
+    for (size_t at = 0; (at = text.find(old, at)) != std::string::npos; at += now.size()) text.replace(at, 4, now);
+  }
+  return text;
+}
+
 void test_overlaps() {
   const uintptr_t B = 0x7400'0000'0000ull;
   auto one = [&](std::vector<Span> v, const char *text) {
     for (Span &s : v) s.lo += B, s.hi += B;
     overlaps_agree(v);
-    const int rc = hdfs_wire::check_overlaps(v);
+    int rc = hdfs_wire::check_overlaps(v);  // the defaults
     CHECK(text ? rc == HDFS_CRC32C_EINVAL && err_is(text) : rc == 0);
+    for (const SpanNouns &nouns : kNouns) {  // the same entries whatever the ranges are called
+      Span sw{}, so{};
+      rc = hdfs_wire::check_overlaps(v, &sw, &so, nouns);
+      CHECK(text ? rc == HDFS_CRC32C_EINVAL && err_is(with_nouns(text, nouns).c_str()) : rc == 0);
+      CHECK(!text || (sw.wire && meet(sw, so)));  // the ranges at fault: a written one and what it overlaps
+    }
   };
   one({}, nullptr);
   one({{0, 10, 0, 1}}, nullptr);
@@ -778,6 +880,7 @@ void test_overlaps() {
   one({{5, 6, 0, 0}, {5, 9, 1, 1}}, "entry 1: wire overlaps the data of entry 0");
   one({{5, 9, 0, 0}, {5, 6, 1, 1}}, "entry 1: wire overlaps the data of entry 0");
   one({{5, 9, 2, 1}, {5, 6, 1, 1}}, "entry 2: wire overlaps the wire of entry 1");
+  one({{5, 9, 7, 0}, {5, 6, 7, 1}}, "entry 7: wire overlaps the data of entry 7");  // a read into its own stream
   // a long wire range swallows later spans that end long before it does
   one({{0, 100, 0, 1}, {100, 110, 1, 1}, {110, 120, 2, 0}}, nullptr);
   one({{0, 100, 0, 1}, {200, 210, 1, 1}, {220, 230, 2, 0}, {240, 250, 3, 1}, {90, 91, 4, 0}},
@@ -1146,6 +1249,289 @@ void test_tail_and_run() {
   F.fail_launch = 0;
 }
 
+
+// ---- the read side: the probed run ---------------------------------------------------------------
+void test_probed_run() {
+  hipStream_t st = nullptr;
+  hipEvent_t ev[2] = {nullptr, nullptr};
+  TablePair tab;
+  CHECK(tab.reserve(4096, kTableFloor) == 0);
+  const uint8_t *pin = tab.pin.as<uint8_t>(), *dv = tab.dev.as<uint8_t>();
+  int launches = 0;
+  auto launch = [&] {
+    F.called("launches");
+    launches++;
+    return F.fail_launch && launches == F.fail_launch ? hipErrorLaunchFailure : hipSuccess;
+  };
+  auto run = [&](int iters, double *ms) {
+    launches = 0;
+    F.copies.clear();
+    return probed_run(st, tab, 64, 160, 1024, 4096, ev, iters, ms, "read batch", launch);
+  };
+  // the plain call: the upload, one round, the copy back, the synchronise; no event call
+  size_t at = F.log.size();
+  CHECK(run(0, nullptr) == 0 && launches == 1);
+  CHECK(names_since(at) == "hipMemcpyAsync launches hipMemcpyAsync hipStreamSynchronize");
+  CHECK(F.copies.size() == 2 && F.copies[0].dst == dv + 64 && F.copies[0].src == pin + 64 && F.copies[0].n == 160 &&
+        F.copies[0].kind == hipMemcpyHostToDevice);
+  CHECK(F.copies[1].dst == pin + 1024 && F.copies[1].src == dv + 1024 && F.copies[1].n == 4096 - 1024 &&
+        F.copies[1].kind == hipMemcpyDeviceToHost);
+  // the timing call: the copy back stays between the first round and the first event
+  for (int iters : {1, 3}) {
+    double ms = -1;
+    at = F.log.size();
+    CHECK(run(iters, &ms) == 0 && launches == 1 + iters && ms == 6.0 / iters && F.copies.size() == 2);
+    std::string want = "hipMemcpyAsync launches hipMemcpyAsync hipEventRecord";
+    for (int i = 0; i < iters; i++) want += " launches";
+    CHECK(names_since(at) == want + " hipEventRecord hipStreamSynchronize hipEventElapsedTime");
+  }
+  // a failing upload: no launch, still synchronised
+  double ms = 0;
+  F.fail_async = 1;
+  at = F.log.size();
+  CHECK(run(2, &ms) == HDFS_CRC32C_EHIP && err_is("read batch: fake: out of memory") && launches == 0 && ms == 0);
+  CHECK(names_since(at) == "hipMemcpyAsync hipStreamSynchronize");
+  // ... a failing copy back: no event
+  F.fail_async = 2;
+  at = F.log.size();
+  CHECK(run(2, &ms) == HDFS_CRC32C_EHIP && err_is("read batch: fake: out of memory") && launches == 1 && ms == 0);
+  CHECK(names_since(at) == "hipMemcpyAsync launches hipMemcpyAsync hipStreamSynchronize");
+  // a launch failing at the first call: nothing comes back
+  F.fail_launch = 1;
+  at = F.log.size();
+  CHECK(run(3, &ms) == HDFS_CRC32C_EHIP && err_is("read batch: fake: launch failure") && ms == 0);
+  CHECK(names_since(at) == "hipMemcpyAsync launches hipStreamSynchronize");
+  // ... and at the second round of the timed loop: no second event, no time read
+  F.fail_launch = 3;
+  at = F.log.size();
+  CHECK(run(3, &ms) == HDFS_CRC32C_EHIP && err_is("read batch: fake: launch failure") && ms == 0);
+  CHECK(names_since(at) ==
+        "hipMemcpyAsync launches hipMemcpyAsync hipEventRecord launches launches hipStreamSynchronize");
+  F.fail_launch = 0;
+  // a failing synchronise after a clean queue, plain and timed
+  for (int iters : {0, 2}) {
+    F.fail_sync = 1;
+    at = F.log.size();
+    CHECK(run(iters, iters ? &ms : nullptr) == HDFS_CRC32C_EHIP && err_is("read batch: fake: launch failure") && ms == 0);
+    CHECK(names_since(at).find("hipEventElapsedTime") == std::string::npos && F.log.back() == "hipStreamSynchronize@0");
+  }
+  F.sticky = hipSuccess;  // the fake's record of the failures above; the run clears nothing, as before
+  // a timing call's own arguments, before any runtime call
+  at = F.log.size();
+  CHECK(timing_args_ok(0, &ms) == HDFS_CRC32C_EINVAL && err_is("iters >= 1 and ms_per_iter are needed"));
+  CHECK(timing_args_ok(-1, &ms) == HDFS_CRC32C_EINVAL && timing_args_ok(1, nullptr) == HDFS_CRC32C_EINVAL);
+  CHECK(err_is("iters >= 1 and ms_per_iter are needed") && timing_args_ok(1, &ms) == 0 && F.log.size() == at);
+  tab.release();
+}
+
+// ---- the read side: the entries' outcomes ------------------------------------------------------------
+void test_outcomes() {
+  {
+    Outcomes o;
+    o.note(0);
+    o.note(3);
+    o.note(fail(-2, "a"));
+    o.note(fail(-5, "b"));
+    o.note(1);
+    fail(-9, "something later");
+    CHECK(o.result() == -2 && err_is("a"));
+  }
+  {
+    Outcomes o;
+    for (int r : {0, 4, 0, 2}) o.note(r);
+    fail(-9, "left alone");
+    CHECK(o.result() == 4 && err_is("left alone"));
+  }
+  {
+    Outcomes o;
+    for (int i = 0; i < 5; i++) o.note(0);
+    CHECK(o.result() == 0 && Outcomes{}.result() == 0);
+  }
+  // slot s of entry b: no slot, or a descriptor that names b back; entry_of is not asked about anything else
+  const uint32_t entry[3] = {5, 6, 7}, none = 0xFFFFFFFFu;
+  int asked = 0;
+  auto of = [&](uint32_t s) { return asked++, entry[s]; };
+  CHECK(slot_adds_up(none, none, 3, 6, of) && asked == 0);
+  CHECK(slot_adds_up(1, none, 3, 6, of) && !slot_adds_up(1, none, 3, 5, of) && asked == 2);
+  CHECK(!slot_adds_up(3, none, 3, 6, of) && !slot_adds_up(1, none, 1, 6, of) && !slot_adds_up(none - 1, none, 3, 6, of));
+  CHECK(asked == 2 && tables_fail(1023) == HDFS_CRC32C_EHIP);
+  CHECK(err_is("internal: the probe's tables do not add up at entry 1023"));
+}
+
+// ---- the read side: the main library's read with unlimited record room ------------------------------
+void test_read_unlimited() {
+  std::vector<hdfs_crc32c_packet> recs;
+  const void *stream = reinterpret_cast<const void *>(uintptr_t(0x7800'0000'0000ull));
+  const hdfs_crc32c_iovec iov[2] = {{nullptr, 0}, {nullptr, 0}};
+  size_t np = 0;
+  uint64_t used = 0, got = 0;
+  auto read = [&](uint64_t len, hdfs_crc32c_packet *own, size_t own_room) {
+    F.reads.clear();
+    np = used = got = 0;
+    return read_unlimited(recs, stream, len, 2, 512, 2, 11, 22, iov, 2, own, own_room, &np, &used, &got);
+  };
+  // 10 000 records in a stream that could hold 20 002: 4 096 do not do, 16 times as many would, cut to the most
+  F.read_records = 10000;
+  CHECK(read(25 * 20000, nullptr, 0) == 0 && np == 10000 && used == 25 * 20000 && got == 77);
+  CHECK(F.reads.size() == 2 && F.reads[0].room == 4096 && F.reads[1].room == 20002 && recs.size() == 20002);
+  CHECK(F.reads[1].pkts == recs.data() && recs[9999].offset_in_block == 10999);
+  for (const Fake::Read &r : F.reads)
+    CHECK(r.stream == stream && r.len == 25 * 20000 && r.client_offset == 11 && r.read_len == 22 && r.iov == iov &&
+          r.iovcnt == 2);
+  // ... that could hold 200 002: 65 536 are enough
+  CHECK(read(25 * 200000, nullptr, 0) == 0 && np == 10000);
+  CHECK(F.reads.size() == 2 && F.reads[0].room == 4096 && F.reads[1].room == 65536);
+  // it ends when the records did not fill the room, and when the room is the most the stream can hold
+  F.read_records = 4095;
+  CHECK(read(25 * 200000, nullptr, 0) == 0 && np == 4095 && F.reads.size() == 1 && F.reads[0].room == 4096);
+  F.read_records = 100;
+  CHECK(read(100, nullptr, 0) == 0 && np == 6 && F.reads.size() == 1 && F.reads[0].room == 6);  // 100 / 25 + 2
+  F.read_records = 70000;
+  CHECK(read(25 * 69998, nullptr, 0) == 0 && np == 70000 && F.reads.size() == 3 && F.reads[2].room == 70000);
+  // a packet error is an answer; an engine failure stops it at once
+  F.read_records = 10000;
+  F.read_rc = 7;
+  CHECK(read(25 * 20000, nullptr, 0) == 7 && np == 10000 && F.reads.size() == 2);
+  F.read_rc = -5;
+  CHECK(read(25 * 20000, nullptr, 0) == -5 && F.reads.size() == 1 && np == 0);
+  F.read_rc = 0;
+  // with the caller's record array: one call, with the caller's room, however many records there are
+  std::vector<hdfs_crc32c_packet> pkts(4 * 8);
+  const size_t b = 3, max_pkts = 8;
+  CHECK(read(25 * 20000, pkts.data() + b * max_pkts, max_pkts) == 0 && np == 8 && F.reads.size() == 1);
+  CHECK(F.reads[0].pkts == pkts.data() + 24 && F.reads[0].room == 8 && pkts[31].offset_in_block == 1007);
+  F.read_records = 0;
+}
+
+// ---- the read side: the main library's walk in pieces -------------------------------------------------
+void test_walk_pieces() {
+  std::vector<hdfs_crc32c_packet> recs;
+  const uint8_t *s = reinterpret_cast<const uint8_t *>(uintptr_t(0x7900'0000'0000ull));
+  struct Seen {
+    uint64_t at, stream_off;
+  };
+  std::vector<Seen> seen;
+  auto walk = [&](std::vector<Fake::Piece> pieces, uint64_t len) {
+    F.pieces = pieces;
+    F.parses.clear();
+    seen.clear();
+    return walk_pieces(recs, 4, s, len, 9, 2, 512, 2,
+                       [&](const hdfs_crc32c_packet &k, uint64_t at) { seen.push_back(Seen{at, k.stream_off}); });
+  };
+  // two full pieces, then the empty last packet: every piece starts where the one before stopped
+  Walk w = walk({{0, 4, 400, false}, {0, 4, 400, false}, {0, 2, 150, true}}, 1000);
+  CHECK(w.rc == 0 && w.pos == 950 && w.npkts == 10 && w.payload == 90 && w.offset_in_block == 4096 + 1000);
+  CHECK(F.parses.size() == 3 && F.parses[1].stream == s + 400 && F.parses[1].len == 600 && F.parses[2].stream == s + 800);
+  CHECK(F.parses[0].room == 4 && recs.size() == 4 && seen.size() == 10 && seen[4].at == 400 && seen[4].stream_off == 0 &&
+        seen[9].at == 800 && seen[9].stream_off == 100);
+  // the empty last packet at the end of a full piece: no further call
+  w = walk({{0, 4, 400, true}, {0, 1, 1, false}}, 1000);
+  CHECK(w.rc == 0 && w.pos == 400 && w.npkts == 4 && w.payload == 30 && F.parses.size() == 1);
+  // a piece shorter than its room (an incomplete packet behind it)
+  w = walk({{0, 4, 400, false}, {0, 3, 300, false}, {0, 1, 1, false}}, 1000);
+  CHECK(w.rc == 0 && w.pos == 700 && w.npkts == 7 && w.payload == 70 && F.parses.size() == 2);
+  // a framing error: the packet that raises it is counted, not handed on, and the walk stops
+  w = walk({{0, 4, 400, false}, {3, 4, 380, false}, {0, 1, 1, false}}, 1000);
+  CHECK(w.rc == 3 && w.pos == 780 && w.npkts == 8 && w.payload == 70 && seen.size() == 7 && F.parses.size() == 2);
+  // an engine failure: its rc, its text behind the entry and the call; what was walked stays
+  F.engine_text = "no memory";
+  w = walk({{0, 4, 400, false}, {-4, 0, 0, false}}, 1000);
+  CHECK(w.rc == -4 && err_is("entry 9: parse_packets: no memory") && w.npkts == 4 && w.pos == 400 && w.payload == 40);
+  CHECK(w.offset_in_block == 4096 + 1000);
+  // a full piece that used no byte ends the walk; the stream's end does; an empty stream is not walked
+  w = walk({{0, 4, 0, false}, {0, 1, 1, false}}, 1000);
+  CHECK(w.rc == 0 && w.pos == 0 && w.npkts == 4 && F.parses.size() == 1);
+  w = walk({{0, 4, 400, false}, {0, 4, 400, false}}, 800);
+  CHECK(w.rc == 0 && w.pos == 800 && w.npkts == 8 && F.parses.size() == 2);
+  w = walk({}, 0);
+  CHECK(w.rc == 0 && w.pos == 0 && w.npkts == 0 && w.payload == 0 && w.offset_in_block == 0 && F.parses.empty());
+  CHECK(kPieceRecords == 65536);
+}
+
+// ---- the read side: the scratch of a library that runs the fused round -----------------------------------
+struct MoreScratch : ReadScratch<FusedState> {  // as the relay library builds its own
+  DeviceBuffer more;
+  int reserve(int to, size_t tab_bytes) {
+    return ReadScratch::reserve(to, tab_bytes, [this] { more.release(); });
+  }
+};
+
+void test_read_scratch() {
+  const size_t live = F.blocks.size();
+  ReadScratch<FusedState> s;
+  F.cur = 0;
+  g_prepares = 0;
+  size_t at = F.log.size();
+  CHECK(s.reserve(0, 100) == 0 && g_prepares == 1 && s.dev == 0 && s.fused.ready && s.tab.dev.cap == kTableFloor);
+  CHECK(names_since(at) == "hipStreamCreate hipMalloc hipMemcpy hipDeviceGetAttribute prepare hipMalloc hipHostMalloc");
+  at = F.log.size();
+  CHECK(s.reserve(0, 16384) == 0 && s.reserve(0, 0) == 0 && F.log.size() == at && g_prepares == 1);  // a warm call
+  // the engine moved to device 2: everything released on device 0, then built again
+  F.cur = 2;
+  at = F.log.size();
+  CHECK(s.reserve(2, 100) == 0 && g_prepares == 2 && s.fused.ready && F.wrong_device_frees == 0);
+  std::string got;
+  for (size_t i = at; i < F.log.size(); i++) got += F.log[i] + " ";
+  CHECK(got == "hipGetDevice@2 hipSetDevice@0 hipStreamSynchronize@0 hipFree@0 hipFree@0 hipHostFree@0 "
+               "hipStreamDestroy@0 hipSetDevice@2 hipStreamCreate@2 hipMalloc@2 hipMemcpy@2 hipDeviceGetAttribute@2 "
+               "prepare@2 hipMalloc@2 hipHostMalloc@2 ");
+  // a failing prepare: EHIP, the text, bound but not ready; the next call prepares again
+  F.cur = 1;
+  g_prepare_rc = hipErrorLaunchFailure;
+  CHECK(s.reserve(1, 100) == HDFS_CRC32C_EHIP && err_is("tables: fake: launch failure") && !s.fused.ready && s.dev == 1);
+  CHECK(!s.tab.dev.p && F.wrong_device_frees == 0);
+  g_prepare_rc = hipSuccess;
+  at = F.log.size();
+  CHECK(s.reserve(1, 100) == 0 && s.fused.ready);
+  CHECK(names_since(at) == "hipMemcpy hipDeviceGetAttribute prepare hipMalloc hipHostMalloc");
+  s.unbind([&] {
+    s.fused.release();
+    s.tab.release();
+  });
+  // a library's further buffers go with the rest, behind them
+  MoreScratch m;
+  F.cur = 0;
+  CHECK(m.reserve(0, 100) == 0 && m.more.reserve(10, 0) == 0);
+  F.cur = 2;
+  at = F.log.size();
+  CHECK(m.reserve(2, 100) == 0 && !m.more.p && F.wrong_device_frees == 0);
+  got.clear();
+  for (size_t i = at; i < F.log.size(); i++) got += F.log[i] + " ";
+  CHECK(got.rfind("hipGetDevice@2 hipSetDevice@0 hipStreamSynchronize@0 hipFree@0 hipFree@0 hipHostFree@0 hipFree@0 "
+                  "hipStreamDestroy@0 hipSetDevice@2 ", 0) == 0);
+  m.unbind([&] {
+    m.fused.release();
+    m.tab.release();
+  });
+  F.cur = 0;
+  CHECK(F.blocks.size() == live && F.streams == 0 && F.wrong_device_frees == 0);
+}
+
+// ---- the read side: where the streams lie -------------------------------------------------------------
+struct StreamEntry {
+  const void *stream;
+  uint64_t len;
+};
+
+void test_stream_places() {
+  const uintptr_t A = 0x7A00'0000'0000ull, H = 0x7B00'0000'0000ull;
+  auto ptr = [](uintptr_t a) { return reinterpret_cast<const void *>(a); };
+  fake_block(A, 4096, 0);
+  fake_block(H, 4096, 0, true);
+  StreamEntry e[3] = {{ptr(A), 4096}, {ptr(H), 0}, {ptr(A + 100), 100}};  // streams may overlap; no bytes, any address
+  F.n.clear();
+  CHECK(check_stream_places(e, 3, 0) == 0 && F.n["hipPointerGetAttributes"] == 1);
+  e[2].len = 3997;
+  char want[256];
+  std::snprintf(want, sizeof(want), "entry 2: stream: 3997 bytes at %p run past the end of their device allocation", ptr(A + 100));
+  CHECK(check_stream_places(e, 3, 0) == HDFS_CRC32C_EINVAL && err_is(want));
+  e[1].len = 8;
+  std::snprintf(want, sizeof(want), "entry 1: stream: %p is not device memory", ptr(H));
+  CHECK(check_stream_places(e, 3, 0) == HDFS_CRC32C_EINVAL && err_is(want));
+  F.blocks.erase(A);
+  F.blocks.erase(H);
+}
+
 }  // namespace
 
 int main() {
@@ -1162,6 +1548,12 @@ int main() {
   test_batch_front_end();
   test_args_and_grid();
   test_tail_and_run();
+  test_probed_run();
+  test_outcomes();
+  test_read_unlimited();
+  test_walk_pieces();
+  test_read_scratch();
+  test_stream_places();
   CHECK(F.blocks.empty() && F.streams == 0 && F.events == 0 && F.wrong_device_frees == 0 && F.sticky == hipSuccess);
   CHECK(F.plans_destroyed - destroyed == 8);  // once for every call above that was given a plan
   std::printf("%d failures\n", g_fail);

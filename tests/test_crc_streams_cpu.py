@@ -144,7 +144,15 @@ def test_sources_include_the_shared_code_and_copy_none():
         assert re.search(r"HDFS_CRC_STREAMS_HD \w+ " + re.escape(name), look), name
         assert not re.search(r"\w+ " + re.escape(name) + r"[^;]*\{", kern), name
     assert "hip" not in look.lower().replace("__hipcc__", "").replace("__hip_device_compile__", "")
-    assert host.count("hdfs_crc32c_parse_packets(") == 1 and "hdfs_crc32c_read_packets" not in host
+    # (through walk_pieces of read_batch_host.h, which also holds the run)
+    shared = code("read_batch_host.h")
+    assert host.count("walk_pieces(") == 1 and "hdfs_crc32c_parse_packets(" not in host
+    assert shared.count("hdfs_crc32c_parse_packets(") == 1 and "hdfs_crc32c_read_packets" not in host
+    for call in ("hipStreamSynchronize(", "hipEventRecord(", "hipEventElapsedTime("):
+        assert call not in host, call
+    assert '#include "read_batch_host.h"' in host and host.count("probed_run(") == 1
+    assert shared.count("hipMemcpyHostToDevice, st)") == 1 and shared.count("hipMemcpyDeviceToHost, st)") == 1
+    assert shared.count("hipMemcpyAsync(") == 2 and shared.count("hipStreamSynchronize(") == 1
     # no CRC arithmetic of a stream's chunks on the host: the host multiplies nothing, it applies the operator to blocks
     assert "mulmod(" not in host and "zeros_op(lens[i], poly).apply(acc)" in host
 

@@ -403,23 +403,27 @@ def test_refusals_leave_the_arena_untouched_and_name_the_entry(engine, rb, oracl
         arr = rb.entries(b) if n <= 4 else (rb.Entry * n)()
         rc = lib.hdfs_read_batch_read_blocks(arr, n, proto, cs, ctype, pk, 8, None)
         return rc, lib.hdfs_read_batch_last_error().decode()
+    # (kw, text, exact): exact texts are asserted whole, the others as a part.  Of the overlap cases "inside stream 1"
+    # provokes exactly one overlapping pair.  The other two provoke two each, of which one is named: a range of this
+    # size laid over the last byte of dst 0 reaches over the guard bytes into dst 1 as well, and one laid back from
+    # the first byte of stream 1 reaches into stream 0 as well.
     cases = {
-        "a host stream in entry 3": (dict(stream3=host.ctypes.data), "entry 3"),
-        "a host destination in entry 2": (dict(dst2=host.ctypes.data), "entry 2"),
-        "stream 0 past its allocation": (dict(stream0=end - a.lens[0] + 1), "entry 0"),
-        "destination 3 past its allocation": (dict(dst3=end - a.caps[3] + 1), "entry 3"),
-        "destination 2 overlaps destination 0": (dict(dst2=p + a.dst[0] + a.caps[0] - 1), "entry 2"),
-        "destination 3 inside stream 1": (dict(dst3=p + a.src[1] + 10), "entry 3"),
-        "destination 1 overlaps its own stream": (dict(dst1=p + a.src[1] - a.caps[1] + 1), "entry 1"),
-        "chunk_size 0": (dict(cs=0), "chunk_size"),
-        "CSUM_NULL": (dict(ctype=0), "CRC32"),
-        "proto 3": (dict(proto=3), "proto"),
-        "no entries": (dict(n=0), "no entries"),
-        "too many entries": (dict(n=rb.MAX_ENTRIES + 1), "1024"),
+        "a host stream in entry 3": (dict(stream3=host.ctypes.data), "entry 3", False),
+        "a host destination in entry 2": (dict(dst2=host.ctypes.data), "entry 2", False),
+        "stream 0 past its allocation": (dict(stream0=end - a.lens[0] + 1), "entry 0", False),
+        "destination 3 past its allocation": (dict(dst3=end - a.caps[3] + 1), "entry 3", False),
+        "destination 2 overlaps destination 0": (dict(dst2=p + a.dst[0] + a.caps[0] - 1), "entry 2", False),
+        "destination 3 inside stream 1": (dict(dst3=p + a.src[1] + 10), "entry 3: dst overlaps the stream of entry 1", True),
+        "destination 1 overlaps its own stream": (dict(dst1=p + a.src[1] - a.caps[1] + 1), "entry 1", False),
+        "chunk_size 0": (dict(cs=0), "chunk_size", False),
+        "CSUM_NULL": (dict(ctype=0), "CRC32", False),
+        "proto 3": (dict(proto=3), "proto", False),
+        "no entries": (dict(n=0), "no entries", False),
+        "too many entries": (dict(n=rb.MAX_ENTRIES + 1), "1024", False),
     }
-    for name, (kw, text) in cases.items():
+    for name, (kw, text, exact) in cases.items():
         rc, err = call(**kw)
-        assert rc == EINVAL and text in err, (name, err)
+        assert rc == EINVAL and (err == text if exact else text in err), (name, err)
         assert bytes(pk) == before and not host.any(), name
     a.check([])
     rc, err = call()  # and the same arguments, unspoilt, work
@@ -436,3 +440,48 @@ def test_c_consumer_runs(engine, tmp_path):
                            "-L", libdir, "-Wl,-rpath," + libdir, "-lhadoofus_read_batch", "-lhadoofus_crc32c"])
     out = subprocess.run([str(exe)], capture_output=True, text=True, timeout=120)
     assert out.returncode == 0 and "0 failures" in out.stdout, out.stdout + out.stderr
+
+
+# ---- a batch at the limit ---------------------------------------------------------------------------------------------
+def test_a_batch_at_the_limit_is_swept_and_refused_by_name(engine, rb, oracle):
+    """1 024 entries of one 512-byte packet and the empty last packet in one
+    arena, the destinations in falling address order, so the overlap sweep
+    has to sort; then one destination at a time is moved onto another range."""
+    n, cap = rb.MAX_ENTRIES, 512 + SLACK
+    kinds = [stream_of(oracle, 2, 2, [512], 300 + k) for k in range(8)]  # entry k reads kinds[k % 8]
+    pays = [_payloads(s, oracle.verify_packets(s)[1]) for s in kinds]
+    slen = len(kinds[0])
+    assert n == 1024 and all(len(s) == slen for s in kinds) and all(len(p) == 512 for p in pays)
+    spitch, dpitch = (slen + 16 + 15) // 16 * 16, cap + 16  # 16 guard bytes at least behind every range
+    src = [GAP + k * spitch for k in range(n)]
+    d0 = GAP + n * spitch + GAP
+    dst = [d0 + (n - 1 - k) * dpitch for k in range(n)]  # entry 0's is the highest
+    buf = engine.DeviceBuffer(d0 + n * dpitch + GAP)
+    image = np.full(buf.nbytes, GUARD, dtype=np.uint8)
+    for k in range(n):
+        image[src[k]:src[k] + slen] = np.frombuffer(kinds[k % 8], dtype=np.uint8)
+    buf.upload(image)
+    p = buf.ptr
+
+    def batch(**moved):
+        return [rb.entry(p + src[k], slen, p + moved.get(f"dst{k}", dst[k]), cap) for k in range(n)]
+    got = rb.read_blocks(batch(), 2, 512, 2, None, None)
+    assert [(g["rc"], g["consumed"], g["delivered"]) for g in got] == [(0, slen, 512)] * n
+    after = buf.download()
+    for k in range(n):
+        assert after[dst[k]:dst[k] + 512].tobytes() == pays[k % 8], k
+        after[dst[k] + 512:dst[k] + cap] = GUARD  # a destination's room behind its payload is unspecified
+        image[dst[k]:dst[k] + 512] = np.frombuffer(pays[k % 8], dtype=np.uint8)
+    assert np.array_equal(after, image)
+    # Where the moved destination overlaps nothing else.  8 bytes into entry 0's destination, the highest range of
+    # the arena: it ends 8 bytes into the 16 guard bytes behind that, ahead of the arena's last GAP bytes.  8 bytes
+    # into a stream: cap + 8 <= slen, so it ends inside that stream.  Its own place stays empty.
+    assert cap + 8 <= slen and dst[0] + 8 + cap <= buf.nbytes
+    lib = rb.load()
+    held = buf.download()
+    for moved, text in ((dict(dst1023=dst[0] + 8), "entry 1023: dst overlaps the dst of entry 0"),
+                        (dict(dst5=src[900] + 8), "entry 5: dst overlaps the stream of entry 900"),
+                        (dict(dst7=src[7] + 8), "entry 7: dst overlaps the stream of entry 7")):
+        rc = lib.hdfs_read_batch_read_blocks(rb.entries(batch(**moved)), n, 2, 512, 2, None, 0, None)
+        assert rc == EINVAL and lib.hdfs_read_batch_last_error().decode() == text, text
+        assert np.array_equal(buf.download(), held), text

@@ -435,25 +435,29 @@ def test_refusals_leave_the_arena_untouched_and_name_the_entry(engine, rl, oracl
         if rc == EINVAL:  # a refusal: every out field zero
             assert all((e.rc, e.consumed, e.delivered, e.wire_len, e.npkts) == (0, 0, 0, 0, 0) for e in arr[:min(n, 4)])
         return rc, lib.hdfs_relay_batch_last_error().decode()
+    # (kw, text, exact): exact texts are asserted whole, the others as a part.  Of the overlap cases "inside stream 1"
+    # provokes exactly one overlapping pair.  The other two provoke two each, of which one is named: a range of this
+    # size laid over the last byte of wire 0 reaches over the guard bytes into stream 2, its neighbour in the shuffled arena, as well, and one laid back from
+    # the first byte of stream 1 reaches into stream 0 as well.
     cases = {
-        "a host stream in entry 3": (dict(stream3=host.ctypes.data), "entry 3"),
-        "a host wire range in entry 2": (dict(wire2=host.ctypes.data), "entry 2"),
-        "stream 0 past its allocation": (dict(stream0=end - len(ss[0]) + 1), "entry 0"),
-        "wire range 3 past its allocation": (dict(wire3=end - a.caps[3] + 1), "entry 3"),
-        "wire range 2 overlaps wire range 0": (dict(wire2=p + a.dst[0] + a.caps[0] - 1), "entry 2"),
-        "wire range 3 inside stream 1": (dict(wire3=p + a.src[1] + 10), "entry 3"),
-        "wire range 1 overlaps its own stream": (dict(wire1=p + a.src[1] - a.caps[1] + 1), "entry 1"),
-        "a negative block offset in entry 2": (dict(off2=-512), "entry 2"),
-        "a negative seqno in entry 1": (dict(seq1=-1), "entry 1"),
-        "chunk_size 0": (dict(cs=0), "chunk_size"),
-        "CSUM_NULL": (dict(ctype=0), "CRC32"),
-        "proto 3": (dict(proto=3), "proto"),
-        "no entries": (dict(n=0), "no entries"),
-        "too many entries": (dict(n=rl.MAX_ENTRIES + 1), "1024"),
+        "a host stream in entry 3": (dict(stream3=host.ctypes.data), "entry 3", False),
+        "a host wire range in entry 2": (dict(wire2=host.ctypes.data), "entry 2", False),
+        "stream 0 past its allocation": (dict(stream0=end - len(ss[0]) + 1), "entry 0", False),
+        "wire range 3 past its allocation": (dict(wire3=end - a.caps[3] + 1), "entry 3", False),
+        "wire range 2 overlaps wire range 0": (dict(wire2=p + a.dst[0] + a.caps[0] - 1), "entry 2", False),
+        "wire range 3 inside stream 1": (dict(wire3=p + a.src[1] + 10), "entry 3: wire overlaps the stream of entry 1", True),
+        "wire range 1 overlaps its own stream": (dict(wire1=p + a.src[1] - a.caps[1] + 1), "entry 1", False),
+        "a negative block offset in entry 2": (dict(off2=-512), "entry 2", False),
+        "a negative seqno in entry 1": (dict(seq1=-1), "entry 1", False),
+        "chunk_size 0": (dict(cs=0), "chunk_size", False),
+        "CSUM_NULL": (dict(ctype=0), "CRC32", False),
+        "proto 3": (dict(proto=3), "proto", False),
+        "no entries": (dict(n=0), "no entries", False),
+        "too many entries": (dict(n=rl.MAX_ENTRIES + 1), "1024", False),
     }
-    for name, (kw, text) in cases.items():
+    for name, (kw, text, exact) in cases.items():
         rc, err = call(**kw)
-        assert rc == EINVAL and text in err, (name, err)
+        assert rc == EINVAL and (err == text if exact else text in err), (name, err)
         assert not host.any(), name
     a.check([b""] * 4)
     rc, err = call()  # and the same arguments, unspoilt, work
@@ -509,3 +513,48 @@ def test_c_consumer_runs(engine, tmp_path):
                            "-L", libdir, "-Wl,-rpath," + libdir, "-lhadoofus_relay_batch", "-lhadoofus_crc32c"])
     out = subprocess.run([str(exe)], capture_output=True, text=True, timeout=120)
     assert out.returncode == 0 and "0 failures" in out.stdout, out.stdout + out.stderr
+
+
+# ---- a batch at the limit ---------------------------------------------------------------------------------------------
+def test_a_batch_at_the_limit_is_swept_and_refused_by_name(engine, rl, oracle):
+    """1 024 entries of one 512-byte packet and the empty last packet in one
+    arena, the wire ranges in falling address order, so the overlap sweep has
+    to sort; then one wire range at a time is moved onto another range."""
+    n = rl.MAX_ENTRIES
+    kinds = [stream_of(oracle, 2, 2, [512], 300 + k) for k in range(8)]  # entry k relays kinds[k % 8]
+    wires = [write_of(oracle, read_of(oracle, s, 2, 2)[2], 0, 0, 2, 2, True)[0] for s in kinds]
+    slen, wlen = len(kinds[0]), len(wires[0])
+    assert n == 1024 and all(len(s) == slen for s in kinds) and all(len(w) == wlen for w in wires)
+    cap = wlen + SLACK
+    # behind every stream, room for a wire range laid 8 bytes into it, and 16 guard bytes at least behind every range
+    spitch, dpitch = (max(slen, 8 + cap) + 16 + 15) // 16 * 16, cap + 16
+    src = [GAP + k * spitch for k in range(n)]
+    d0 = GAP + n * spitch + GAP
+    dst = [d0 + (n - 1 - k) * dpitch for k in range(n)]  # entry 0's is the highest
+    buf = engine.DeviceBuffer(d0 + n * dpitch + GAP)
+    image = np.full(buf.nbytes, GUARD, dtype=np.uint8)
+    for k in range(n):
+        image[src[k]:src[k] + slen] = np.frombuffer(kinds[k % 8], dtype=np.uint8)
+    buf.upload(image)
+    p = buf.ptr
+
+    def batch(**moved):
+        return [rl.entry(p + src[k], slen, p + moved.get(f"wire{k}", dst[k]), cap, 0, 0, True) for k in range(n)]
+    got = rl.relay(batch(), 2, 512, 2)
+    assert [(g["rc"], g["consumed"], g["delivered"], g["wire_len"]) for g in got] == [(0, slen, 512, wlen)] * n
+    for k in range(n):
+        image[dst[k]:dst[k] + wlen] = np.frombuffer(wires[k % 8], dtype=np.uint8)
+    held = buf.download()
+    assert np.array_equal(held, image)
+    # Where the moved wire range overlaps nothing else.  8 bytes into entry 0's wire range, the highest range of the
+    # arena: it ends 8 bytes into the 16 guard bytes behind that, ahead of the arena's last GAP bytes.  8 bytes into
+    # a stream: it ends at most 8 + cap bytes behind the stream's start, and the next stream starts 16 bytes
+    # further at least (spitch).  Its own place stays empty.
+    assert 8 + cap + 16 <= spitch and dst[0] + 8 + cap <= buf.nbytes
+    lib = rl.load()
+    for moved, text in ((dict(wire1023=dst[0] + 8), "entry 1023: wire overlaps the wire of entry 0"),
+                        (dict(wire5=src[900] + 8), "entry 5: wire overlaps the stream of entry 900"),
+                        (dict(wire7=src[7] + 8), "entry 7: wire overlaps the stream of entry 7")):
+        rc = lib.hdfs_relay_batch_relay(rl.entries(batch(**moved)), n, 2, 512, 2, None)
+        assert rc == EINVAL and lib.hdfs_relay_batch_last_error().decode() == text, text
+        assert np.array_equal(buf.download(), held), text

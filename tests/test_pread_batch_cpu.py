@@ -102,7 +102,8 @@ def test_sources_share_the_round_and_the_layout_and_copy_none():
         assert f'#include "{inc}"' in kern, inc
     for inc in ("read_batch_layout.h", "crc32c_frame.h"):
         assert f'#include "{inc}"' in lay, inc
-    for inc in ("companion_support.h", "wire_fused_host.h", "wire_fused_tables.h", "pread_batch_layout.h"):
+    for inc in ("companion_support.h", "read_batch_host.h", "wire_fused_host.h", "wire_fused_tables.h",
+                "pread_batch_layout.h"):
         assert f'#include "{inc}"' in host, inc
     # the layout header is host and device arithmetic with no HIP runtime call
     assert "HDFS_HD" in lay and not re.search(r"\bhip[A-Z]\w*\(", lay)
@@ -129,7 +130,17 @@ def test_sources_share_the_round_and_the_layout_and_copy_none():
     for name in ("write_of(pk0, nw, g, k)", "load_round(", "store_round(", "store16(", "store8(", "range_of(",
                  "address_space(4)", "kNowhere", "probe_window("):
         assert name in kern, name
-    assert host.count("hdfs_crc32c_read_packets(") >= 1 and host.count("hipMemcpyAsync(") == 2
+    # the run, the outcomes and the main library's read are the shared header's, once for the six libraries
+    shared = "\n".join(l for l in read("read_batch_host.h").splitlines() if not l.lstrip().startswith("//"))
+    for call in ("hipMemcpyAsync(", "hipStreamSynchronize(", "hipEventRecord(", "hipEventElapsedTime(",
+                 "hdfs_crc32c_read_packets("):
+        assert call not in host, call
+    assert '#include "read_batch_host.h"' in host and host.count("probed_run(") == 1
+    assert host.count("read_unlimited(") == 1 and shared.count("hdfs_crc32c_read_packets(") == 2  # own room; grown
+    assert shared.count("hipMemcpyHostToDevice, st)") == 1 and shared.count("hipMemcpyDeviceToHost, st)") == 1
+    assert shared.count("hipMemcpyAsync(") == 2 and shared.count("hipStreamSynchronize(") == 1
+    # the overlap check is the one sweep of companion_support.h; this file defines none
+    assert host.count("check_overlaps(") == 1 and "struct Span" not in host and "far_d" not in host
     assert "x.client_offset, x.read_len" in host and "READ_ALL, &iov" not in host
 
 

@@ -130,9 +130,10 @@ def test_the_pread_batch_library_is_unchanged():
         "pread_batch_internal.h", "pread_batch_layout.h", "read_batch_layout.h", "read_batch_verify.h",
         "wire_fused_batch_lookup.h", "wire_fused_round.h", "wire_fused_crc.h", "wire_fused_tables.h",
         "wire_fused_host.h", "wire_internal.h", "crc32c_frame.h", "crc32c_outpkt.h", "crc32c_tables.h",
-        "companion_support.h", "pread_batch_exports.map"]
+        "companion_support.h", "read_batch_host.h", "pread_batch_exports.map"]
     assert not set(build.PREAD_BATCH_HEADERS + build.PREAD_BATCH_SOURCES) & set(OWN + ["preadv_batch_exports.map"])
-    want = {"pread_batch_kernels.hip": "f32110dd5b28e30a5f5c9775af47e36bd34e6efa4efe77b62180dde49ee2fac0", "pread_batch.cpp": "8c768ebcc0f9190fbb4a0af553948dfa20aceb1480e9492956939d9fe9c8d5e3", "pread_batch_internal.h": "def77bed855b7d4ffaf5195f39a7c3689c098a057847aa8a90c25281669b8638",
+    # (pread_batch.cpp has since moved onto the read side's shared host header, read_batch_host.h)
+    want = {"pread_batch_kernels.hip": "f32110dd5b28e30a5f5c9775af47e36bd34e6efa4efe77b62180dde49ee2fac0", "pread_batch_internal.h": "def77bed855b7d4ffaf5195f39a7c3689c098a057847aa8a90c25281669b8638",
             "pread_batch_layout.h": "c684bcccc86fc1f2dcde9341fa56f8edd29421d68341569567ec8da779a73ab6", "read_batch_verify.h": "bc5664e6208aa6992fc11c2f96dc82f4c17a62323bc938581d848dc61376b0e1"}
     for f, digest in want.items():
         assert hashlib.sha256(open(os.path.join(build.CSRC, f), "rb").read()).hexdigest() == digest, f
@@ -148,7 +149,8 @@ def test_sources_share_the_round_the_layout_and_the_lookups_and_copy_none():
                 "pread_batch_layout.h", "read_batch_verify.h", "read_batch_header.h", "preadv_batch_lookup.h",
                 "preadv_batch_internal.h"):
         assert f'#include "{inc}"' in kern, inc
-    for inc in ("companion_support.h", "wire_fused_host.h", "wire_fused_tables.h", "pread_batch_layout.h"):
+    for inc in ("companion_support.h", "read_batch_host.h", "wire_fused_host.h", "wire_fused_tables.h",
+                "pread_batch_layout.h"):
         assert f'#include "{inc}"' in host, inc
     assert '#include "wirev_fused_internal.h"' in code("preadv_batch_internal.h")
     # the four lookups' texts stay where they are, in files of their own, comments included
@@ -182,9 +184,18 @@ def test_sources_share_the_round_the_layout_and_the_lookups_and_copy_none():
                  "tail_edge(", "unseamed("):
         assert len(re.findall(r"HDFS_WIREV_FUSED_HD \w+ " + re.escape(name), look)) == 1, name
         assert not re.search(r"(inline|FUSED_DEV|HD) \w+ " + re.escape(name), kern), name
-    assert host.count("hdfs_crc32c_read_packets(") >= 1 and host.count("hipMemcpyAsync(") == 2
-    assert host.count("hipStreamSynchronize(") == 1 and "x.read_len, x.iov," in host and "x.iovcnt" in host
-    assert "std::sort(" in host  # the overlap check is one sort and sweep
+    # the run, the outcomes and the main library's read are the shared header's, once for the six libraries
+    shared = "\n".join(l for l in read("read_batch_host.h").splitlines() if not l.lstrip().startswith("//"))
+    for call in ("hipMemcpyAsync(", "hipStreamSynchronize(", "hipEventRecord(", "hipEventElapsedTime(",
+                 "hdfs_crc32c_read_packets("):
+        assert call not in host, call
+    assert '#include "read_batch_host.h"' in host and host.count("probed_run(") == 1
+    assert host.count("read_unlimited(") == 1 and shared.count("hdfs_crc32c_read_packets(") == 2  # own room; grown
+    assert shared.count("hipMemcpyHostToDevice, st)") == 1 and shared.count("hipMemcpyDeviceToHost, st)") == 1
+    assert shared.count("hipMemcpyAsync(") == 2 and shared.count("hipStreamSynchronize(") == 1
+    assert "x.read_len, x.iov," in host and "x.iovcnt" in host
+    # the overlap check is the one sweep of companion_support.h; this file defines none
+    assert host.count("check_overlaps(") == 1 and "struct Span" not in host and "far_d" not in host
 
 
 # ---- ABI -------------------------------------------------------------------------------------

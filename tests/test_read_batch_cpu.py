@@ -91,7 +91,8 @@ def test_sources_include_the_shared_code_and_copy_none():
     for inc in ("wire_fused_round.h", "wire_fused_batch_lookup.h", "crc32c_frame.h", "crc32c_outpkt.h",
                 "read_batch_layout.h"):
         assert f'#include "{inc}"' in kern, inc
-    for inc in ("companion_support.h", "wire_fused_host.h", "wire_fused_tables.h", "read_batch_layout.h"):
+    for inc in ("companion_support.h", "read_batch_host.h", "wire_fused_host.h", "wire_fused_tables.h",
+                "read_batch_layout.h"):
         assert f'#include "{inc}"' in host, inc
     helpers = ["range_of(", "load16(", "store16(", "store32(", "load8(", "store8(", "fold8(", "transpose(", "unit_of(",
                "load_round(", "store_round(", "crc_round(", "header(", "ragged_chunk(", "ragged_finish(",
@@ -109,7 +110,17 @@ def test_sources_include_the_shared_code_and_copy_none():
                  "prefix_regular(", "address_space(4)", "put_out_header("):
         assert name in kern or name in lay, name
     assert "frame_step(" in lay and "hipMalloc" not in lay and "hipLaunch" not in lay and "hipMemcpy" not in lay
-    assert host.count("hdfs_crc32c_read_packets(") >= 1 and host.count("hipMemcpyAsync(") == 2
+    # the run, the outcomes and the main library's read are the shared header's, once for the six libraries
+    shared = "\n".join(l for l in read("read_batch_host.h").splitlines() if not l.lstrip().startswith("//"))
+    for call in ("hipMemcpyAsync(", "hipStreamSynchronize(", "hipEventRecord(", "hipEventElapsedTime(",
+                 "hdfs_crc32c_read_packets("):
+        assert call not in host, call
+    assert '#include "read_batch_host.h"' in host and host.count("probed_run(") == 1
+    assert "HDFS_CRC32C_READ_ALL, &iov, 1" in host and host.count("read_unlimited(") == 1 and shared.count("hdfs_crc32c_read_packets(") == 2  # own room; grown
+    assert shared.count("hipMemcpyHostToDevice, st)") == 1 and shared.count("hipMemcpyDeviceToHost, st)") == 1
+    assert shared.count("hipMemcpyAsync(") == 2 and shared.count("hipStreamSynchronize(") == 1
+    # the overlap check is the one sweep of companion_support.h; this file defines none
+    assert host.count("check_overlaps(") == 1 and "struct Span" not in host and "far_d" not in host
 
 
 # ---- ABI -------------------------------------------------------------------------------------

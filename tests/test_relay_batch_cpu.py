@@ -129,7 +129,8 @@ def test_sources_include_the_shared_code_and_copy_none():
     for inc in ("relay_batch_lookup.h", "relay_batch_internal.h", "read_batch_layout.h", "read_batch_header.h",
                 "read_batch_verify.h", "wire_fused_batch_lookup.h", "wire_fused_round.h", "crc32c_outpkt.h"):
         assert f'#include "{inc}"' in kern, inc
-    for inc in ("companion_support.h", "hadoofus_relay_batch.h", "wire_fused_batch_internal.h", "wire_fused_host.h",
+    for inc in ("companion_support.h", "read_batch_host.h", "hadoofus_relay_batch.h", "wire_fused_batch_internal.h",
+                "wire_fused_host.h",
                 "wire_layout.h", "relay_batch_lookup.h"):
         assert f'#include "{inc}"' in host, inc
     every = "".join(read(f) for f in sorted(os.listdir(build.CSRC)))
@@ -163,8 +164,18 @@ def test_sources_include_the_shared_code_and_copy_none():
         assert re.search(r"HDFS_RELAY_HD \w+ " + re.escape(name), look), name
         assert not re.search(r"(inline|FUSED_DEV|HD) \w+ " + re.escape(name) + r"[^;]*\{", kern), name
     # the fallback: the main library's read, then the fused batch write library's launch over wire_layout.h's layout
-    assert host.count("hdfs_crc32c_read_packets(") == 1 and "launch_frame_fused_batch(" in host
-    assert "build_layout(" in host and host.count("hipStreamSynchronize(") == 1
+    # (read_unlimited of read_batch_host.h, which also holds the run: this file synchronises through it and through
+    # sync_and_report alone)
+    shared = code("read_batch_host.h")
+    assert host.count("read_unlimited(") == 1 and "hdfs_crc32c_read_packets(" not in host
+    assert shared.count("hdfs_crc32c_read_packets(") == 2 and "launch_frame_fused_batch(" in host  # own room; grown
+    assert "build_layout(" in host and "hipStreamSynchronize(" not in host and host.count("probed_run(") == 1
+    for call in ("hipEventRecord(", "hipEventElapsedTime("):
+        assert call not in host, call
+    assert shared.count("hipMemcpyHostToDevice, st)") == 1 and shared.count("hipMemcpyDeviceToHost, st)") == 1
+    assert shared.count("hipMemcpyAsync(") == 2 and shared.count("hipStreamSynchronize(") == 1
+    # the overlap check is the one sweep of companion_support.h; this file defines none
+    assert host.count("check_overlaps(") == 1 and "struct Span" not in host and "far_d" not in host
     # no existing source changes for it: the fused batch write library's kernel file is the one that library builds
     assert "wire_fused_batch_kernels.hip" in build.WIRE_FUSED_BATCH_SOURCES
 
